@@ -67,6 +67,8 @@ def parse():
                                                             "output gradient instead of the sampling step (no CLIP leg, no update)")
     p.add_argument("--rehearse", action="store_true", help="launcher / collective rehearsal without the model: every rank joins the process group "
                                                             "(gloo when there is no GPU), all-gathers a small tensor and rank 0 prints a JSON line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, rank 0 writes what the last timed step returned "
+                                                                       "(all ranks' shares) as DIR/<name>.npy, float32")
     return p.parse_args()
 
 
@@ -273,6 +275,8 @@ def main_sd(a, rank, world, dev, dist):
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"latents": lat}, rank, world, dist)
     if rank != 0:
         return
     step_ms_dev = sum(s.elapsed_time(e) for s, e in ev) / a.steps
@@ -312,6 +316,31 @@ def main_sd(a, rank, world, dev, dist):
         out["parity"] = {"eps_max_abs_err": float((got - want).abs().max()), "eps_max_abs": float(want.abs().max()),
                          "sample": f"batch 1, {sres}x{sres} latents, index 600, vs the CPU fp32 oracle (pinned on the reference's vendored CompVis UNet, tests/golden/sd_ldm_*.npz)"}
     print(json.dumps(out), flush=True)
+
+
+DUMP_MAX_BYTES = 63 * 10**6      # element bytes: with the .npy headers (128 bytes a file) under 64 MB in all
+
+
+def dump_outputs(d, outputs, rank, world, dist):
+    """--dump-outputs: every rank's share of each output (batch-sharded chains) gathered to rank 0, in rank order, and written as
+    d/<name>.npy in float32.  Above DUMP_MAX_BYTES in all, each output is cut to the same fraction of its elements, picked by a fixed
+    seed, so that runs with the same arguments still compare element for element.  Runs after the timed region."""
+    import numpy as np
+    if dist is not None:
+        for k, v in outputs.items():
+            got = [torch.empty_like(v) for _ in range(world)]
+            dist.all_gather(got, v.contiguous())
+            outputs[k] = torch.cat(got)
+    if rank != 0:
+        return
+    os.makedirs(d, exist_ok=True)
+    outputs = {k: v.detach().float().cpu() for k, v in outputs.items()}
+    total = sum(v.numel() * 4 for v in outputs.values())
+    for k, v in outputs.items():
+        if total > DUMP_MAX_BYTES:
+            keep = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:v.numel() * DUMP_MAX_BYTES // total]
+            v = v.reshape(-1)[keep.sort().values]
+        np.save(os.path.join(d, k + ".npy"), v.numpy())
 
 
 def conv_kernel_name(desc):
@@ -380,7 +409,7 @@ def main():
             pred = pred.guided(grad, guidance_scale=0.5, clamp_value=1e-6)
         return pred.step(ti)
     eager_step = one_step
-    tape_gb = None
+    tape_gb = input_grad = None
     if a.backward:
         # what a script differentiating through the UNet pays per evaluation (losses/velocity_diffusion.py:33-61 guided_resample_; upstream
         # GuidedDiffusion.predicted_noise under autograd, guided_diffusion.py:125-133): training-mode forward + backward to the input
@@ -400,7 +429,7 @@ def main():
                     tensors(v, seen)
 
         def one_step(images, i, model=model):   # noqa: F811
-            nonlocal tape_gb
+            nonlocal tape_gb, input_grad
             fi, _ = sched[i % len(sched)]
             if is_v:
                 if cond is not None:
@@ -412,7 +441,7 @@ def main():
                 seen = {}
                 tensors(tape, seen)
                 tape_gb = sum(seen.values()) / 1e9
-            g = model.engine.backward(tape, probe, sdict)
+            input_grad = model.engine.backward(tape, probe, sdict)
             return images
 
     if a.graph:
@@ -466,6 +495,8 @@ def main():
             raise SystemExit(f"process group has {dist.get_world_size()} ranks, --gpus {a.gpus}")
     finite = bool(torch.isfinite(images).all().item())
     checksum = float(images.double().abs().sum().item())     # same schedule and seed -> comparable between --graph / --chains / eager runs
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"input_grad": input_grad} if a.backward else {"images": images}, rank, world, dist)
 
     if rank == 0:
         step_ms_dev = sum(s.elapsed_time(e) for s, e in ev) / a.steps

@@ -654,9 +654,21 @@ def gen_tokenizer():
     -- the identity is what ftfy.fix_text returns for well-formed ASCII text, so no arithmetic of the path is replaced."""
     import types
     sys.modules.setdefault("ftfy", types.SimpleNamespace(fix_text=lambda t: t))
-    tk = R.ref("models.slip.tokenizer").SimpleTokenizer()
+    T = R.ref("models.slip.tokenizer")
+    tk = T.SimpleTokenizer()
     ids = torch.stack([tk(p) for p in TOKENIZER_PROMPTS])
     save("clip_tokenizer", ids=ids, lengths=np.array([len(tk.encode(p)) for p in TOKENIZER_PROMPTS]))
+    # the merge list itself is not stored: only the merges (with their ranks) whose joined symbol is a substring of a pre-token of the
+    # prompts -- every pair BPE can form on these prompts is such a substring, so the other merges cannot change their ids
+    subs = set()
+    for p in TOKENIZER_PROMPTS:
+        for piece in T.re.findall(tk.pat, T.whitespace_clean(T.basic_clean(p)).lower()):
+            w = "".join(tk.byte_encoder[b] for b in piece.encode("utf-8"))
+            subs.update(w[i:j] for i in range(len(w)) for j in range(i + 1, len(w) + 1))
+            subs.update(w[i:] + "</w>" for i in range(len(w)))
+    keep = sorted((r, m) for m, r in tk.bpe_ranks.items() if "".join(m) in subs)
+    save("clip_tokenizer_merges", merges=np.array([m for _, m in keep]), ranks=np.array([r for r, _ in keep]),
+         n_merges=np.array(len(tk.bpe_ranks)))
 
 
 if __name__ == "__main__" and len(sys.argv) > 1:

@@ -1,7 +1,5 @@
 """CPU: host-side logic of the drop-in classes (schedules, shapes, packing, resize tables, error behaviour)
 against the reference's golden vectors.  No HIP compute."""
-import os
-
 import pytest
 import torch
 
@@ -178,17 +176,18 @@ def test_velocity_diffusion_and_clip_state_dicts():
     assert c.device.type == "cpu" and c.engine is None
 
 
-REF_BPE = "/root/reference/perceptor/models/slip/bpe_simple_vocab_16e6.txt.gz"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_BPE), reason="the CLIP merge list is data that is not part of this repository (build container only)")
 def test_clip_tokenizer_matches_reference_ids():
-    """perceptor_amd.utils.tokenizer against ids the reference's own tokenizer produced (oracle/gen_golden.py: gen_tokenizer), reading the
-    merge list (data, 48 894 merges) from where it lies in the reference tree; skipped where that tree is absent."""
+    """perceptor_amd.utils.tokenizer against ids the reference's own tokenizer produced (oracle/gen_golden.py: gen_tokenizer).  The merge
+    list (data, 48 894 merges) is not part of this repository: the fixture holds, at their ranks, the merges whose joined symbol occurs in
+    a pre-token of the prompts, which are all a merge of these prompts can use; every other rank holds a pair no text can form."""
     from oracle.gen_golden import TOKENIZER_PROMPTS
     from perceptor_amd.utils.tokenizer import ClipTokenizer
     g = golden("clip_tokenizer")
-    tk = ClipTokenizer(REF_BPE)
+    gm = golden("clip_tokenizer_merges")
+    merges = [(f"\0{r}", "\0") for r in range(int(gm["n_merges"]))]     # "\0" is no symbol of the byte alphabet
+    for m, r in zip(gm["merges"].tolist(), gm["ranks"].tolist()):
+        merges[r] = tuple(m)
+    tk = ClipTokenizer(merges=merges)
     assert tk.vocab_size == 49408 and (tk.sot, tk.eot) == (49406, 49407)
     for i, p in enumerate(TOKENIZER_PROMPTS):
         assert len(tk.encode(p)) == int(g["lengths"][i])
