@@ -101,12 +101,19 @@ def _check(got, ref, dtype, extra=1.0):
     dict(n=8, h=16, w=16, cin=1024, cout=1024, k=3, res_up=True),          # up ResBlock tail on a small map: the reduce kernel adds nearest-up(skip)
 ])
 def test_igemm_conv(case, dtype):
-    from perceptor_amd.engine import ops
     from perceptor_amd import _hip
-    from perceptor_amd._hip import dtype_code
-    dev = _dev()
     # small unit shapes would otherwise be routed to the generic kernel (grid-fill heuristic): force the halo tile configs
     _hip.lib().pmi_set_option(1, case.get("force_cfg", -1))
+    try:
+        _igemm_conv_case(case, dtype)
+    finally:
+        _hip.lib().pmi_set_option(1, -1)
+
+
+def _igemm_conv_case(case, dtype):
+    from perceptor_amd.engine import ops
+    from perceptor_amd._hip import dtype_code
+    dev = _dev()
     g = torch.Generator().manual_seed(0)
     n, h, w, cin, cout, k = (case[z] for z in ("n", "h", "w", "cin", "cout", "k"))
     x = _r(torch.randn(n, cin, h, w, generator=g), dtype)
@@ -145,7 +152,6 @@ def test_igemm_conv(case, dtype):
         assert float((got - ref).abs().max()) <= tol
     else:
         _check(out[..., :cout].permute(0, 3, 1, 2).cpu(), ref, dtype)
-    _hip.lib().pmi_set_option(1, -1)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -416,8 +422,10 @@ def test_fused_output_statistics_feed_groupnorm(case, dtype):
     lin2 = ops.PackedLinear(torch.randn(64, cin, k, k, generator=g) / (cin * k * k) ** 0.5, torch.randn(64, generator=g), dt, dev)
     from perceptor_amd import _hip
     _hip.lib().pmi_set_option(1, case.get("force_cfg", -1))
-    y = ops.igemm(x, lin, want_stats=True)
-    _hip.lib().pmi_set_option(1, -1)
+    try:
+        y = ops.igemm(x, lin, want_stats=True)
+    finally:
+        _hip.lib().pmi_set_option(1, -1)
     y2 = ops.igemm(x, lin2, want_stats=True)
     assert hasattr(y, "_pmi_stats") and hasattr(y2, "_pmi_stats")
     gamma, beta = (1 + 0.1 * torch.randn(cout + 64, generator=g)).to(dev), (0.1 * torch.randn(cout + 64, generator=g)).to(dev)

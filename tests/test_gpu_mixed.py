@@ -98,10 +98,10 @@ def test_conv3x3_mixed_vs_torch(case, operand):
     sp = case.get("split")
     x0 = xs.to(DEV) if sp is None else to_split(x[..., :sp]).to(DEV)
     x1 = None if sp is None else to_split(x[..., sp:]).to(DEV)
-    if case["cfg"] >= 0:
-        _hip.lib().pmi_set_option(1, case["cfg"])
     ops.MIXED_TRACE = []
     try:
+        if case["cfg"] >= 0:
+            _hip.lib().pmi_set_option(1, case["cfg"])
         out = ops.conv3x3_mixed(x0, ml, x1=x1, operand=operand, prologue=(ca.to(DEV), cb.to(DEV), _hip.ACT_SILU), up=up,
                                 residual=res.to(DEV) if res is not None else None, res_up=bool(case.get("res_up")),
                                 nbias=nb.to(DEV) if nb is not None else None)
