@@ -309,6 +309,25 @@ int pmi_vit_assemble(const float* emb, const float* cls, const float* pos, float
 int pmi_spherical_loss(const float* emb, const float* tgt, const float* wts, float* loss, float* demb, int N, int K, int D,
                        int n_total, float mult, float gscale, pmi_stream_t s);
 
+/* ---- CLIP ModifiedResNet image tower (open_clip / OpenAI-CLIP RN50 .. RN50x64; csrc/resnet.hip) ------------------------------------------
+ * The reference runs open_clip's model.encode_image + autograd (models/open_clip.py:109-123, RN towers of models/open_clip.py:24-44 and
+ * models/clip.py:6-27).  Convolutions (BatchNorm folded into weight + bias), their input gradients, pools and ReLU masks are pmi_igemm /
+ * pmi_avgpool2(_bwd) / pmi_act_fwd / pmi_act_bwd; these replace the rest, 16-bit dtype 0 / 1:
+ * Normalize(mean, std) of the resized NCHW fp32 image (models/open_clip.py:78-81) -> the stem convolution's input [N][H][W][8] (channels 3..7 zero);
+ * the adjoint: dimg[n][c][y][x] = mul * dx[n][y][x][c] / std[c], dx fp32 with channel pitch ldc */
+int pmi_rn_stage_input(const float* img, const float* mean, const float* stdv, void* out, int N, int H, int W, int dtype, pmi_stream_t s);
+int pmi_rn_stage_input_bwd(const float* dx, int ldc, const float* stdv, float* dimg, int N, int H, int W, float mul, pmi_stream_t s);
+/* AttentionPool2d's tokens (flatten + torch.cat([mean, x]) + positional_embedding): x [N][HW][C] -> tok [N*(HW+1)][C], the mean in fp32;
+ * the adjoint dx[n][p] = dtok[n][1+p] + (dtok[n][0] + dq0[n]) / HW (dq0 [N][C] fp32: the query path's gradient of row 0, or NULL) */
+int pmi_rn_tokens(const void* x, const float* pos, void* tok, int N, int HW, int C, int dtype, pmi_stream_t s);
+int pmi_rn_tokens_bwd(const void* dtok, const float* dq0, void* dx, int N, int HW, int C, int dtype, pmi_stream_t s);
+/* AttentionPool2d's F.multi_head_attention_forward with the mean token as the only query, head dim 64, T <= 1024 keys:
+ * q [N][C], kv [N*T][2C] (K | V, projections applied) -> o [N][C], P [N*heads][T] fp32 softmax(scale q.k) (kept for the backward);
+ * backward: dO [N][C] -> dq [N][C] (before the scale is applied to q), dkv [N*T][2C] (dK | dV), one workgroup per (image, head) */
+int pmi_rn_attn_fwd(const void* q, const void* kv, void* o, float* P, int N, int T, int C, int heads, float scale, int dtype, pmi_stream_t s);
+int pmi_rn_attn_bwd(const void* q, const void* kv, const float* P, const void* dout, void* dq, void* dkv, int N, int T, int C, int heads,
+                    float scale, int dtype, pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

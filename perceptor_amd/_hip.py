@@ -134,6 +134,13 @@ _PROTOS = {
     "pmi_l2norm_rows": ([_P, _P, _I, _I, _F, _P],),
     "pmi_vit_assemble": ([_P, _P, _P, _P, _I, _I, _I, _I, _P],),
     "pmi_spherical_loss": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P],),
+    # CLIP ResNet towers (resnet.hip)
+    "pmi_rn_stage_input": ([_P, _P, _P, _P, _I, _I, _I, _I, _P],),
+    "pmi_rn_stage_input_bwd": ([_P, _I, _P, _P, _I, _I, _I, _F, _P],),
+    "pmi_rn_tokens": ([_P, _P, _P, _I, _I, _I, _I, _P],),
+    "pmi_rn_tokens_bwd": ([_P, _P, _P, _I, _I, _I, _I, _P],),
+    "pmi_rn_attn_fwd": ([_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],),
+    "pmi_rn_attn_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],),
 }
 
 

@@ -27,6 +27,11 @@ TEXT_CONFIGS = {
     "ViT-B-16": (77, 49408, 512, 12, 8, 512),
     "ViT-L-14": (77, 49408, 768, 12, 12, 768),
     "ViT-H-14": (77, 49408, 1024, 24, 16, 1024),
+    "RN50": (77, 49408, 512, 12, 8, 1024),
+    "RN101": (77, 49408, 512, 12, 8, 512),
+    "RN50x4": (77, 49408, 640, 12, 10, 640),
+    "RN50x16": (77, 49408, 768, 12, 12, 768),
+    "RN50x64": (77, 49408, 1024, 12, 16, 1024),
 }
 
 

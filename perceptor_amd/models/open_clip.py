@@ -1,7 +1,8 @@
 """OpenCLIP / CLIP image encoders — drop-in for perceptor.models.OpenCLIP and perceptor.models.CLIP.
 
 Call surface of perceptor/models/open_clip.py:12-140 and perceptor/models/clip.py:6-27.  The ViT image
-tower runs in perceptor_amd.engine.vit.VitEngine (HIP); pre-processing is the reference's:
+towers run in perceptor_amd.engine.vit.VitEngine, the ResNet towers (RN50 .. RN50x64) in
+perceptor_amd.engine.resnet.ResNetEngine (HIP); pre-processing is the reference's:
 resize (ResizeRight lanczos3/bicubic) -> Normalize(mean, std) -> tower -> F.normalize.
 
 The text tower (``encode_texts``, models/open_clip.py:99-107) runs in perceptor_amd.engine.text.TextEngine behind
@@ -10,7 +11,7 @@ perceptor_amd.utils.tokenizer.ClipTokenizer; the tokenizer's merge list is data 
 
 Not available here (SURVEY.md §8f-4, stated loudly instead of faked): pretrained weights (no network;
 ``weights="synthetic"`` gives name-keyed deterministic weights, or pass ``checkpoint=`` with an
-open_clip state dict: ``visual.*`` and, for the text side, the root-level text-tower tensors) and ResNet towers.
+open_clip state dict: ``visual.*`` and, for the text side, the root-level text-tower tensors).
 """
 from __future__ import annotations
 
@@ -19,6 +20,7 @@ from typing import Optional
 import torch
 
 from .._hip import call, ptr
+from ..engine import resnet
 from ..engine import text as text_engine
 from ..engine import vit
 from ..utils.param_tree import ParamTree
@@ -71,12 +73,14 @@ class _EncodeImages(torch.autograd.Function):
 class OpenCLIP(torch.nn.Module):
     def __init__(self, architecture="ViT-H-14", weights="laion2b_s32b_b79k", precision=None, *, checkpoint: Optional[str] = None,
                  seed: int = 0, quick_gelu: Optional[bool] = None, config: Optional[tuple] = None, text_config: Optional[tuple] = None,
-                 bpe_path: Optional[str] = None):
+                 bpe_path: Optional[str] = None, rn_config: Optional[tuple] = None):
         """
         Args:
             architecture (str): name of the clip model
             weights (str): name of the weights ("synthetic" for deterministic offline weights)
             precision (str): "bf16" (default on HIP) or "fp16"
+            config: a ViT image tower (image, patch, width, layers, heads, out_dim) registered under the architecture's name
+            rn_config: a ResNet image tower (image, (layers x 4), width, heads, out_dim) registered under the architecture's name
         """
         super().__init__()
         self.architecture, self.weights = architecture, weights
@@ -85,11 +89,17 @@ class OpenCLIP(torch.nn.Module):
         base = architecture.replace("-quickgelu", "")
         if config is not None:
             vit.VIT_CONFIGS.setdefault(base, tuple(config))
-        if base not in vit.VIT_CONFIGS:
+        if rn_config is not None:
+            res_, layers_, *rest = rn_config
+            resnet.RN_CONFIGS.setdefault(base, (res_, tuple(layers_), *rest))
+        if base in vit.VIT_CONFIGS:
+            self.kind, self.cfg = "vit", vit.VIT_CONFIGS[base]
+        elif base in resnet.RN_CONFIGS:
+            self.kind, self.cfg = "resnet", resnet.RN_CONFIGS[base]
+        else:
             if weights == "synthetic":
                 raise ValueError(f"Invalid architecture/weights: {architecture}/{weights}")
-            raise NotImplementedError(f"{architecture}: only the ViT image towers {sorted(vit.VIT_CONFIGS)} run on the HIP path")
-        self.cfg = vit.VIT_CONFIGS[base]
+            raise NotImplementedError(f"{architecture}: only the image towers {sorted(vit.VIT_CONFIGS) + sorted(resnet.RN_CONFIGS)} run on the HIP path")
         if weights != "synthetic" and checkpoint is None:
             raise RuntimeError(f"pretrained weights {architecture}/{weights} cannot be downloaded (no network): "
                                "pass checkpoint=<visual state dict> or weights='synthetic'")
@@ -100,9 +110,10 @@ class OpenCLIP(torch.nn.Module):
             warnings.warn("precision='fp32' requested: the HIP CLIP tower multiplies in bf16 on the MFMA (fp32 accumulation, fp32 residual "
                           "stream, LayerNorm and softmax); embedding rel-L2 error vs fp32 ~4e-3 (tests/test_gpu_clip.py)", RuntimeWarning, stacklevel=2)
         self.precision = {None: "bf16", "fp16": "f16", "f16": "f16", "bf16": "bf16", "fp32": "bf16"}[precision]
-        shapes = vit.vit_state_dict_shapes(self.cfg)
+        shapes = vit.vit_state_dict_shapes(self.cfg) if self.kind == "vit" else resnet.rn_state_dict_shapes(self.cfg)
         # text tower (context, vocab, width, layers, heads, out_dim): open_clip's config of the architecture, or text_config=
-        self.text_cfg = tuple(text_config) if text_config is not None else (text_engine.TEXT_CONFIGS.get(base) if config is None else None)
+        custom = config is not None or rn_config is not None
+        self.text_cfg = tuple(text_config) if text_config is not None else (text_engine.TEXT_CONFIGS.get(base) if not custom else None)
         tshapes = text_engine.text_state_dict_shapes(self.text_cfg) if self.text_cfg is not None else {}
         if checkpoint is not None:
             raw = torch.load(checkpoint, map_location="cpu", weights_only=True)
@@ -118,11 +129,11 @@ class OpenCLIP(torch.nn.Module):
             tsd = synth_state_dict(tshapes, seed) if tshapes else {}
         # the reference holds the open_clip model as self.model: image tower under "visual.", text tower at its root (models/open_clip.py:65-76)
         self.model = ParamTree({**{"visual." + k: v for k, v in sd.items()}, **tsd})
-        self._engine: Optional[vit.VitEngine] = None
+        self._engine = None                   # vit.VitEngine or resnet.ResNetEngine, packed on first use
         self._text_engine: Optional[text_engine.TextEngine] = None
         self._tokenizer, self._bpe_path = None, bpe_path
         self.register_load_state_dict_post_hook(lambda module, incompatible: (setattr(module, "_engine", None), setattr(module, "_text_engine", None)))
-        self.output_dim = self.cfg[5]
+        self.output_dim = self.cfg[5] if self.kind == "vit" else self.cfg[4]
 
     def visual_state_dict(self):
         return {k[len("visual."):]: v for k, v in self.model.state_dict().items() if k.startswith("visual.")}
@@ -140,9 +151,12 @@ class OpenCLIP(torch.nn.Module):
         return self._text_engine
 
     @property
-    def engine(self) -> Optional[vit.VitEngine]:
+    def engine(self):
         if self._engine is None and self.device.type == "cuda":
-            self._engine = vit.VitEngine(self.cfg, self.visual_state_dict(), self.device, self.precision, self.quick_gelu)
+            if self.kind == "vit":
+                self._engine = vit.VitEngine(self.cfg, self.visual_state_dict(), self.device, self.precision, self.quick_gelu)
+            else:                             # (ModifiedResNet has no GELU: quick_gelu concerns its text tower only)
+                self._engine = resnet.ResNetEngine(self.cfg, self.visual_state_dict(), self.device, self.precision)
         return self._engine
 
     def _apply(self, fn, *a, **k):

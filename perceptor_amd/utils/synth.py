@@ -50,8 +50,16 @@ def synth_tensor(name: str, shape: Sequence[int], seed: int = 0, gain: float = 1
     elif len(shape) >= 2:
         fan_in = int(np.prod(shape[1:]))
         w = z * (gain * float(fan_in) ** -0.5)   # gain < 1 keeps deep norm-free nets (wikiart) inside the fp16 range
+    elif leaf == "weight" and name.endswith(".bn3.weight") and "layer" in name:
+        # the last BatchNorm of a CLIP ResNet Bottleneck (its residual branch): gains around 0.5 keep the residual stream bounded through
+        # 33-64 blocks (at 1.0 it grows to rms ~23 in RN50x64 and the attention pool's softmax degenerates into an argmax)
+        w = 0.5 * (1.0 + 0.1 * z)
     elif leaf in ("weight",):  # norm gains
         w = 1.0 + 0.1 * z
+    elif leaf == "running_var":  # BatchNorm statistics (CLIP ResNet towers): a variance must be positive
+        w = 0.5 + np.abs(z)
+    elif leaf == "running_mean":
+        w = 0.1 * z
     else:  # biases and other vectors
         w = 0.05 * z
     if len(shape) >= 2 and rounding == "bf16":
