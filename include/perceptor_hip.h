@@ -26,9 +26,12 @@ int pmi_abi_version(void);
 
 /* ---- implicit-GEMM convolution / GEMM on MFMA ----------------------------------
  * D[m][n] = act(alpha * sum_k A(m,k) * B[n][k] + bias[n] + nbias[m / hw][n]) + R[m][n]
- * conv mode (taps == 9, stride 2, or up): m = (img, y, x) over the OUTPUT grid H x W,
+ * conv mode (taps 9 or 16, stride 2, or up): m = (img, y, x) over the OUTPUT grid H x W,
  * k = tap * Cin + c; A(m,k) gathers pixel (y*stride + dy, x*stride + dx) of the
- * (optionally nearest-2x upsampled) input with zero padding.  Channels [0,C0) come
+ * (optionally nearest-2x upsampled) input with zero padding.  taps 9: dy, dx in -1..1
+ * (3x3); taps 16 (stride 2 only, Hin = 2H, Win = 2W): dy = tap/4 - 1, dx = tap%4 - 1 in
+ * -1..2, the 4x4 window of the input gradient of nearest-x2 + conv3x3 (Upsample2D) with
+ * phase-folded weights.  Channels [0,C0) come
  * from A0, [C0,C0+C1) from A1 (skip-concat without materialising torch.cat).
  * Replaces: nn.Conv2d 3x3 / 1x1 / Conv1d k=1 / nn.Linear / einsum-bmm in
  *   guided_diffusion/unet.py:232-252 (ResBlock), :294-300 (AttentionBlock qkv/proj),
@@ -50,7 +53,7 @@ typedef struct {
   int32_t lda0, lda1;  /* elements between consecutive pixels/rows of A0 / A1 */
   int32_t ldb, ldd, ldr;
   int32_t H, W, Hin, Win; /* conv mode only */
-  int32_t taps;        /* 1 or 9 */
+  int32_t taps;        /* 1, 9 or 16 */
   int32_t stride;      /* 1 or 2 */
   int32_t up;          /* nearest x2 upsample of the input (Hin = H/2) */
   int32_t res_up;      /* residual is an [H/2 x W/2] grid read at (y>>1, x>>1): nearest x2 upsample of the skip path */

@@ -12,6 +12,8 @@
 // so both the ds_write_b128 staging and the ds_read_b128 fragment reads are conflict-free.
 // Global->LDS goes through registers (gathered addresses + zero fill for the conv halo);
 // the loads of k-tile t+1 are issued before the MFMAs of tile t and written after them.
+// Conv taps: 9 = 3x3 (dy, dx in -1..1); 16 = the 4x4 stride-2 window (dy, dx in -1..2) of the
+// Upsample2D adjoint, whose weights are the 3x3 kernel folded per output phase (engine/sd.py).
 #include <cstdio>
 #include <cstdlib>
 #include "common.h"
@@ -115,6 +117,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
       const uint32_t so = (uint32_t)(cbase - (second ? a.C0 : 0)) * 2u;
       int dy = 0, dx = 0;
       if (CONV && a.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
+      if (CONV && a.taps == 16) { dy = (tap >> 2) - 1; dx = (tap & 3) - 1; }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         uint32_t vo;
@@ -140,6 +143,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
     const int cc = second ? ci - a.C0 : ci;
     int dy = 0, dx = 0;
     if (CONV && a.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
+    if (CONV && a.taps == 16) { dy = (tap >> 2) - 1; dx = (tap & 3) - 1; }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       uint4 v = make_uint4(0, 0, 0, 0);
@@ -510,7 +514,7 @@ template <typename T>
 int launch(const pmi_igemm_args& a, hipStream_t s) {
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   const dim3 grid(tiles, 1, a.batch > 1 ? a.batch : (a.splitk > 1 ? a.splitk : 1)), block(256);
-  const bool conv = a.taps == 9 || a.up || a.stride == 2;
+  const bool conv = a.taps != 1 || a.up || a.stride == 2;
   const int Cin = a.C0 + a.C1;
   const bool kfast = (Cin % BK == 0) && (a.C0 % BK == 0);
   if (conv) {
@@ -624,7 +628,9 @@ extern "C" int pmi_igemm(const pmi_igemm_args* a, pmi_stream_t stream) {
   if ((a->N & 3) && (a->bias || a->nbias || a->R || a->ldd < ((a->N + 3) & ~3))) return bad_arg(__LINE__);
   if ((a->lda0 & 7) || (a->ldb & 7) || (a->ldd & 3)) return bad_arg(__LINE__);
   if (a->C1 > 0 && (!a->A1 || (a->lda1 & 7))) return bad_arg(__LINE__);
-  if (a->taps != 1 && a->taps != 9) return bad_arg(__LINE__);
+  if (a->taps != 1 && a->taps != 9 && a->taps != 16) return bad_arg(__LINE__);
+  // taps 16: the 4x4 stride-2 window of the Upsample2D adjoint (rows / columns 2y-1 .. 2y+2 of the high-resolution gradient)
+  if (a->taps == 16 && (a->stride != 2 || a->up || a->res_up || a->Hin != 2 * a->H || a->Win != 2 * a->W)) return bad_arg(__LINE__);
   if (a->stride != 1 && a->stride != 2) return bad_arg(__LINE__);
   if (a->K != a->taps * (a->C0 + a->C1)) return bad_arg(__LINE__);
   if (a->R && (a->ldr & 3)) return bad_arg(__LINE__);
@@ -634,7 +640,7 @@ extern "C" int pmi_igemm(const pmi_igemm_args* a, pmi_stream_t stream) {
   // check behind the config query below rejects every other route)
   if (a->split_in == 2 && !a->split_out) return bad_arg(__LINE__);
   if (a->nbias && a->hw <= 0) return bad_arg(__LINE__);
-  const bool conv = a->taps == 9 || a->up || a->stride == 2;
+  const bool conv = a->taps != 1 || a->up || a->stride == 2;
   if (a->res_up && ((a->H & 1) || (a->W & 1))) return bad_arg(__LINE__);
   if ((conv || a->res_up) && (a->H <= 0 || a->W <= 0 || a->Hin <= 0 || a->Win <= 0 || a->M % (a->H * a->W))) return bad_arg(__LINE__);
   if (a->up && (a->H != 2 * a->Hin || a->W != 2 * a->Win)) return bad_arg(__LINE__);

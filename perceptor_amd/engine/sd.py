@@ -19,6 +19,7 @@ so a real checkpoint's tensors load as they are.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -137,6 +138,51 @@ def unet_gflop(cfg: SdConfig, h: int, w: int, tc: int = 77) -> float:
                 hh, ww = hh * 2, ww * 2
                 fl += 2.0 * hh * ww * l[2] * l[2] * 9
     return fl / 1e9
+
+
+def vae_decoder_gflop(cfg: "VaeConfig", h: int, w: int, fused_up: bool = True) -> Tuple[float, float]:
+    """Algorithmic GFLOP (2 per multiply-add) of ONE VAE decode of ONE sample at h x w latents: (forward, input-gradient backward).
+    Forward: convolutions, linears and the mid attention's two products.  Backward: every convolution's dX (the same MFMA work as its
+    forward), the attention's four products (dP, dV, dQ, dK) and both projections; the up-samplers' adjoints cost 16 taps at the low
+    resolution when fused (16 / 36 of their forward) or their forward count when composed.  GroupNorm / SiLU / softmax are not counted."""
+    lc, top, bo = cfg.latent_channels, cfg.block_out[-1], cfg.block_out
+    hh, ww = h, w
+    res = lambda hw, ci, co: 2.0 * hw * (ci * co * 9 + co * co * 9 + (ci * co if ci != co else 0))
+    fwd = 2.0 * hh * ww * lc * lc + 2.0 * hh * ww * lc * top * 9
+    fwd += 2 * res(hh * ww, top, top)
+    t = hh * ww
+    proj = 2.0 * t * top * top * 4                                     # q | k | v and proj_attn
+    fwd += proj + 4.0 * t * t * top
+    bwd = fwd + 4.0 * t * t * top                                      # four t x t x C products instead of two
+    ch = top
+    up_b = 0.0
+    for i, o in enumerate(reversed(bo)):
+        for _ in range(cfg.layers_per_block + 1):
+            f = res(hh * ww, ch, o)
+            fwd += f; bwd += f
+            ch = o
+        if i != len(bo) - 1:
+            f = 2.0 * (4 * hh * ww) * o * o * 9
+            fwd += f
+            up_b += (2.0 * hh * ww * o * o * 16) if fused_up else f
+            hh, ww = 2 * hh, 2 * ww
+    f = 2.0 * hh * ww * ch * cfg.out_channels * 9
+    fwd += f; bwd += f + up_b
+    return fwd / 1e9, bwd / 1e9
+
+
+def fold_upsample_weights(weight: torch.Tensor) -> torch.Tensor:
+    """Weights of the one-pass adjoint of Upsample2D (nearest x2, then a 3x3 convolution with padding 1).
+
+    With y = conv3x3(up2(x)), dx[p] gathers the rows 2p-1 .. 2p+2 of dy; the kernel rows that reach pixel p from them are
+    {2}, {1, 2}, {0, 1}, {0} (the same per column).  So dx = conv2d(dy, W', stride=2, padding=1) with
+    W'[ci, co, i, j] = sum over ky in S_i, kx in S_j of W[co, ci, ky, kx]: 16 taps per low-resolution pixel instead of 4 x 9.
+    weight [Cout, Cin, 3, 3] -> [Cin, Cout, 4, 4] float64."""
+    w = weight.detach().double()
+    s = ((2,), (1, 2), (0, 1), (0,))
+    rows = torch.stack([w[:, :, list(si), :].sum(2) for si in s], 2)                 # [Cout, Cin, 4, 3]
+    folded = torch.stack([rows[..., list(sj)].sum(-1) for sj in s], 3)                # [Cout, Cin, 4, 4]
+    return folded.permute(1, 0, 2, 3).contiguous()
 
 
 def unet_state_dict_shapes(cfg: SdConfig) -> Dict[str, Tuple[int, ...]]:
@@ -453,6 +499,171 @@ class VaeDecoderEngine(_Blocks):
         out = torch.empty((n, cfg.out_channels, ho, wo), dtype=torch.float32, device=dev)
         mul, add = (0.5, 0.5) if to_images else (1.0, 0.0)          # diffusion_space.decode: (x + 1) / 2
         call("pmi_nhwc_to_nchw", ptr(y), y.shape[-1], ptr(out), n, ho, wo, cfg.out_channels, mul, add)
+        return out
+
+    # ---- input gradient (d loss / d latents through the frozen decoder: loss-guided sampling) -----------------------------------------
+    # forward_train() issues forward()'s launch sequence and keeps the operands of every nonlinear step: per ResnetBlock2D its input x,
+    # the GN1 coefficients and statistics partials, conv1's output h and the GN2 ones; for the mid attention its input, GN, q|k|v and the
+    # softmax P; the last h with its GN.  The up-samplers and every convolution are linear in their input: nothing is kept for them.
+    # backward() walks the tape once.  A convolution's dX is pmi_igemm on transposed, flipped weights; GroupNorm + SiLU backward is
+    # pmi_gn_bwd_*; the attention's is ops.attention_backward on the kept P; an up-sampler's adjoint is one stride-2 4x4-tap pmi_igemm on
+    # phase-folded weights (fold_upsample_weights) instead of dX at the high resolution + pmi_upsample_nearest2_bwd.
+    def _resnet_train(self, k, x, tape, groups, eps):
+        dt, w = self.dt, self.w
+        ca, cb, p1 = ops.group_norm_coeffs_train(x, *w[k + ".gn1"], groups, dt, eps=eps)
+        h = ops.igemm(x, w[k + ".conv1"], prologue=(ca, cb, ACT_SILU), want_stats=True)
+        ca2, cb2, p2 = ops.group_norm_coeffs_train(h, *w[k + ".gn2"], groups, dt, eps=eps)
+        skip = ops.igemm(x, w[k + ".skip"]) if (k + ".skip") in w else x
+        tape.append(("res", k, x, (ca, cb, p1), h, (ca2, cb2, p2)))
+        return ops.igemm(h, w[k + ".conv2"], residual=skip, prologue=(ca2, cb2, ACT_SILU), want_stats=True)
+
+    def _attention_train(self, a, x, tape, groups):
+        dt, w = self.dt, self.w
+        n, h2, w2, cc = x.shape
+        m = n * h2 * w2
+        ca, cb, parts = ops.group_norm_coeffs_train(x, *w[a + ".gn"], groups, dt, eps=1e-6)
+        hn = torch.empty_like(x)
+        call("pmi_gn_apply", ptr(x), None, cc, ptr(ca), ptr(cb), None, ptr(hn), n, h2, w2, cc, ACT_NONE, 0, dt)
+        qkv = ops.igemm(hn.view(m, cc), w[a + ".qkv"])
+        at, pm = ops.attention_train(qkv.view(n, h2 * w2, 3 * cc), 1, dt)       # = ops.attention's batched-GEMM path (head dim > 160)
+        o = ops.igemm(at.view(m, cc), w[a + ".proj"], residual=x.view(m, cc), want_stats=True, hw=h2 * w2)
+        tape.append(("attn", a, x, (ca, cb, parts), qkv, pm))
+        h4 = o.view(n, h2, w2, cc)
+        if hasattr(o, "_pmi_stats"):
+            h4._pmi_stats = o._pmi_stats
+        return h4
+
+    @torch.no_grad()
+    def forward_train(self, latents: torch.Tensor, scale: float = 1.0 / 0.18215, to_images: bool = True):
+        """As forward(), keeping what backward() needs: (images NCHW fp32, tape).  For head dims above 160 (SD-v1: 512) the value equals
+        forward()'s bit for bit; a 64-channel head runs forward()'s d64 kernel there and the batched GEMMs here (rounding-level)."""
+        cfg, dt, dev, w = self.cfg, self.dt, self.device, self.w
+        if not latents.is_cuda:
+            raise RuntimeError("VaeDecoderEngine runs on a HIP device only (no CPU fallback)")
+        latents = latents.float().contiguous()
+        n, c, hh, ww = latents.shape
+        if c != cfg.latent_channels:
+            raise ValueError(f"latents must have {cfg.latent_channels} channels")
+        tdt = _hip.TORCH_DTYPE[dt]
+        x = torch.empty((n, hh, ww, self.pq.cin_p), dtype=tdt, device=dev)
+        call("pmi_nchw_to_nhwc", ptr(latents), ptr(x), n, c, hh, ww, self.pq.cin_p, float(scale), 0.0, dt)
+        z = ops.igemm(x, self.pq)
+        h = ops.igemm(z, self.conv_in, want_stats=True)
+        g, eps = cfg.groups, 1e-6
+        rec: List[tuple] = []
+        h = self._resnet_train("decoder.mid_block.resnets.0", h, rec, g, eps)
+        h = self._attention_train("decoder.mid_block.attentions.0", h, rec, g)
+        h = self._resnet_train("decoder.mid_block.resnets.1", h, rec, g, eps)
+        for kind, k in self.plan:
+            if kind == "res":
+                h = self._resnet_train(k, h, rec, g, eps)
+            else:
+                rec.append(("up", k))
+                h = ops.igemm(h, w[k], up=True, want_stats=True)
+        ca, cb, parts = ops.group_norm_coeffs_train(h, *self.gn_out, g, dt, eps=eps)
+        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
+        _, ho, wo, _ = y.shape
+        out = torch.empty((n, cfg.out_channels, ho, wo), dtype=torch.float32, device=dev)
+        mul, add = (0.5, 0.5) if to_images else (1.0, 0.0)
+        call("pmi_nhwc_to_nchw", ptr(y), y.shape[-1], ptr(out), n, ho, wo, cfg.out_channels, mul, add)
+        tape = {"rec": rec, "last": (h, (ca, cb, parts)), "scale": float(scale), "to_images": bool(to_images),
+                "in_shape": (n, c, hh, ww), "out_shape": (n, cfg.out_channels, ho, wo)}
+        return out, tape
+
+    def _wt(self, key, weight, cin_pad=None, rows=None):
+        """Packed weights of the input-gradient convolution of `weight` [Cout, Cin(, k, k)] ([Cout, Cin] linears): [Cin, Cout, k, k] with
+        both taps flipped; rows: zero-pad its output channels (the forward's zero-padded input channels) to this count."""
+        if key not in self.w:
+            wt = weight.detach().cpu().float()
+            if wt.ndim == 2:
+                wt = wt[:, :, None, None]
+            wt = wt.permute(1, 0, 2, 3).flip(2, 3)
+            if rows is not None and rows > wt.shape[0]:
+                wt = torch.cat([wt, wt.new_zeros((rows - wt.shape[0],) + tuple(wt.shape[1:]))], 0)
+            self.w[key] = PackedLinear(wt.contiguous(), None, self.dt, self.device, cin_pad=cin_pad)
+        return self.w[key]
+
+    def _up_back(self, k, g, sd, fused: bool = True):
+        """Gradient wrt the input of nearest-x2 + conv3x3 from g = gradient wrt its output [N, 2h, 2w, C].  The folded one-pass kernel is
+        the faster one at all three SD-v1 shapes; fused=False runs the composed adjoint for the A/B of the probe."""
+        n, h2, w2, c = g.shape
+        if fused:
+            if k + ".fold" not in self.w:
+                self.w[k + ".fold"] = PackedLinear(fold_upsample_weights(sd[k + ".weight"].cpu()).float(), None, self.dt, self.device)
+            return ops.igemm(g, self.w[k + ".fold"], stride=2)
+        d = ops.igemm(g, self._wt(k + "T", sd[k + ".weight"]))
+        out = torch.empty((n, h2 // 2, w2 // 2, d.shape[-1]), dtype=d.dtype, device=d.device)
+        call("pmi_upsample_nearest2_bwd", ptr(d), ptr(out), n, h2 // 2, w2 // 2, d.shape[-1], self.dt)
+        return out
+
+    def _res_back(self, rec, g, sd, groups, eps):
+        _, k, x, gn1, h, gn2 = rec
+        dt, w = self.dt, self.w
+        d_a2 = ops.igemm(g, self._wt(k + ".conv2T", sd[k + ".conv2.weight"]))                  # wrt SiLU(GN2(h))
+        dh, _ = ops.group_norm_backward(h, d_a2, *gn2, w[k + ".gn2"][0], groups, dt, act=ACT_SILU, eps=eps)
+        d_a1 = ops.igemm(dh, self._wt(k + ".conv1T", sd[k + ".conv1.weight"]))                 # wrt SiLU(GN1(x))
+        gs = ops.igemm(g, self._wt(k + ".skipT", sd[k + ".conv_shortcut.weight"])) if (k + ".skip") in w else g
+        gx, _ = ops.group_norm_backward(x, d_a1, *gn1, w[k + ".gn1"][0], groups, dt, act=ACT_SILU, gadd0=gs, eps=eps)
+        return gx
+
+    def _attn_back(self, rec, g, sd, groups):
+        _, a, x, gn, qkv, pm = rec
+        dt, w = self.dt, self.w
+        n, h2, w2, cc = x.shape
+        t, m = h2 * w2, n * h2 * w2
+        da = ops.igemm(g.view(m, cc), self._wt(a + ".projT", sd[a + ".proj_attn.weight"]))
+        dqkv = ops.attention_backward(qkv.view(n, t, 3 * cc), pm, da.view(n, t, cc), 1, dt)
+        if a + ".qkvT" not in self.w:
+            self._wt(a + ".qkvT", torch.cat([sd[f"{a}.{nm}.weight"].cpu() for nm in ("query", "key", "value")], 0))
+        dhn = ops.igemm(dqkv.view(m, 3 * cc), self.w[a + ".qkvT"]).view(n, h2, w2, cc)
+        gx, _ = ops.group_norm_backward(x, dhn, *gn, w[a + ".gn"][0], groups, dt, act=ACT_NONE, gadd0=g, eps=1e-6)
+        return gx
+
+    @torch.no_grad()
+    def backward(self, tape, d_out: torch.Tensor, state_dict) -> torch.Tensor:
+        """d loss / d latents (NCHW fp32) from d loss / d output (NCHW fp32, the shape forward_train() returned) and its tape.
+        `state_dict`: the decoder's tensors by name (StableDiffusion.vae.state_dict()); the transposed / folded weights are packed from it on
+        the first call and kept on the engine.  f16 engines scale the gradient by a power of two on the way in and back on the way out
+        (image gradients of a CLIP loss are ~1e-6 and would flush to zero in f16); bf16 needs no scaling."""
+        cfg, dt, dev = self.cfg, self.dt, self.device
+        if not d_out.is_cuda:
+            raise RuntimeError("VaeDecoderEngine runs on a HIP device only (no CPU fallback)")
+        if tuple(d_out.shape) != tape["out_shape"]:
+            raise ValueError(f"d_out must have the output's shape {tape['out_shape']}, got {tuple(d_out.shape)}")
+        d_out = d_out.float().contiguous()
+        n, co, ho, wo = tape["out_shape"]
+        sd = state_dict
+        g_, eps = cfg.groups, 1e-6
+        gscale = 1.0
+        if dt == _hip.DT_F16:
+            amax_n = torch.empty((n,), dtype=torch.float32, device=dev)
+            call("pmi_quantile_abs", ptr(d_out), ptr(amax_n), n, co * ho * wo, 1.0)           # per-sample max |d_out|
+            amax = max(amax_n.tolist())
+            if amax > 0.0 and amax == amax and amax != float("inf"):
+                gscale = 2.0 ** max(-24, min(24, -math.ceil(math.log2(amax))))
+        tdt = _hip.TORCH_DTYPE[dt]
+        g = torch.empty((n, ho, wo, 8), dtype=tdt, device=dev)
+        call("pmi_nchw_to_nhwc", ptr(d_out), ptr(g), n, co, ho, wo, 8, (0.5 if tape["to_images"] else 1.0) * gscale, 0.0, dt)
+        h, gn = tape["last"]
+        d_act = ops.igemm(g, self._wt("decoder.conv_outT", sd["decoder.conv_out.weight"], cin_pad=8))
+        g, _ = ops.group_norm_backward(h, d_act, *gn, self.gn_out[0], g_, dt, act=ACT_SILU, eps=eps)
+        for rec in reversed(tape["rec"]):
+            if rec[0] == "res":
+                g = self._res_back(rec, g, sd, g_, eps)
+            elif rec[0] == "attn":
+                g = self._attn_back(rec, g, sd, g_)
+            else:
+                g = self._up_back(rec[1], g, sd)
+        lp = self.pq.cin_p
+        gz = ops.igemm(g, self._wt("decoder.conv_inT", sd["decoder.conv_in.weight"], rows=lp))      # [.., lp]: rows past 4 are zero
+        if "post_quant_convT" not in self.w:                                                       # 1x1, 4 -> 4 padded to lp x lp
+            wq = torch.zeros((lp, lp))
+            wq[:cfg.latent_channels, :cfg.latent_channels] = sd["post_quant_conv.weight"].detach().cpu().float().flatten(1)
+            self._wt("post_quant_convT", wq)
+        gx = ops.igemm(gz, self.w["post_quant_convT"], out_f32=True)                               # [n, h, w, lp] fp32
+        _, c, hh, ww = tape["in_shape"]
+        out = torch.empty((n, c, hh, ww), dtype=torch.float32, device=dev)
+        call("pmi_nhwc_to_nchw", ptr(gx), gx.shape[-1], ptr(out), n, hh, ww, c, tape["scale"] / gscale, 0.0)
         return out
 
 

@@ -40,7 +40,35 @@ def _load(path):
     return {k: v.float() for k, v in torch.load(path, map_location="cpu", weights_only=True).items()}
 
 
+class _Decode(torch.autograd.Function):
+    """decode(latents) with an input gradient, as autograd provides upstream through vae.decode (stable_diffusion.py:195-198): forward and
+    backward are the HIP decoder's forward_train / backward (engine/sd.py).  The VAE is frozen: no parameter gradients."""
+
+    @staticmethod
+    def forward(ctx, latents, model):
+        eng = model._engine("decoder")
+        out, tape = eng.forward_train(latents)
+        ctx.model, ctx.engine, ctx.tape = model, eng, tape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_images):
+        g = ctx.engine.backward(ctx.tape, grad_images.float().contiguous(), ctx.model.vae.state_dict())
+        ctx.tape = None
+        return g, None
+
+
 class StableDiffusion(torch.nn.Module):
+    """Loss-guided sampling: ``decode`` is differentiable with respect to the latents when grad mode is on and they require grad, so any
+    image loss reaches the UNet's latent space as upstream::
+
+        pred = sd.predictions(diffused_latents, from_index, conditioning)
+        dl = pred.denoised_latents.detach().requires_grad_()
+        loss(sd.decode(dl)).backward()
+        diffused_latents = pred.guided(dl.grad).step(to_index)
+
+    Otherwise ``decode`` runs the no-grad decoder (no tape, same bits)."""
+
     def __init__(self, name: str = "runwayml/stable-diffusion-v1-5", decoder_name: Optional[str] = "stabilityai/sd-vae-ft-mse",
                  fp16: bool = True, auth_token=True, flash_attention: bool = True, attention_slicing=None, *,
                  weights: str = "synthetic", unet_checkpoint: Optional[str] = None, vae_checkpoint: Optional[str] = None,
@@ -164,7 +192,11 @@ class StableDiffusion(torch.nn.Module):
         raise ValueError(f"Unknown encoding method {method}")
 
     def decode(self, latents):
-        return self._engine("decoder").forward(latents.to(self.device))
+        eng = self._engine("decoder")
+        latents = latents.to(self.device)
+        if torch.is_grad_enabled() and latents.requires_grad:
+            return _Decode.apply(latents, self)
+        return eng.forward(latents)
 
     @contextmanager
     def finetuneable_vae(self):
