@@ -247,10 +247,7 @@ class AdmEngine:
         qkv = ops.igemm(hn.view(n * hh * ww, c), w[l.p + ".qkv"])
         a = ops.attention(qkv.view(n, hh * ww, 3 * c), l.heads, 1 if self.cfg.use_new_attention_order else 0, dt)
         out = ops.igemm(a.view(n * hh * ww, c), w[l.p + ".proj"], residual=x.view(n * hh * ww, c), want_stats=True, hw=hh * ww)
-        o4 = out.view(n, hh, ww, c)
-        if hasattr(out, "_pmi_stats"):
-            o4._pmi_stats = out._pmi_stats
-        return o4
+        return ops.view_nhwc(out, n, hh, ww)
 
     def _run(self, layers, h, h1, emb):
         for l in layers:
@@ -268,12 +265,11 @@ class AdmEngine:
             h1 = None
         return h
 
-    @torch.no_grad()
-    def forward(self, images: torch.Tensor, timesteps: torch.Tensor, out_channels: Optional[int] = None) -> torch.Tensor:
-        """images: NCHW fp32 in [0,1] (encoded to x = 2*img-1 on the fly); returns NCHW fp32 model output."""
+    def _embed_input(self, images, timesteps):
+        """Time embedding (all emb_layers outputs at once) and the padded NHWC input x = 2 * images - 1: (emb, x)."""
         cfg, dt, dev = self.cfg, self.dt, self.device
         if not images.is_cuda:
-            raise RuntimeError("AdmEngine runs on a HIP device only (no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__} runs on a HIP device only (no CPU fallback)")
         images = images.float().contiguous()
         n, _, hh, ww = images.shape
         t = timesteps.to(device=dev, dtype=torch.float32).contiguous()
@@ -290,43 +286,41 @@ class AdmEngine:
             emb = ops.igemm(e, self.emb_all, out_f32=True)       # [N, sum of all emb_layers outputs]
         x = torch.empty((n, hh, ww, 16 if self.precise else 8), dtype=tdt, device=dev)
         call("pmi_prep_input", ptr(images), None, 0, ptr(x), n, hh, ww, 8, dt)
-        h, hs = x, []
+        return emb, x
+
+    def _output(self, h, ca, cb, out_channels):
+        """conv_out on SiLU(GroupNorm(h)) given the norm's coefficients -> NCHW fp32 model output."""
+        n, hh, ww, _ = h.shape
+        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
+        co = out_channels or self.cfg.out_channels
+        out = torch.empty((n, co, hh, ww), dtype=torch.float32, device=self.device)
+        call("pmi_finish_output", ptr(y), y.shape[-1], ptr(out), n, hh, ww, co)
+        return out
+
+    @torch.no_grad()
+    def forward(self, images: torch.Tensor, timesteps: torch.Tensor, out_channels: Optional[int] = None) -> torch.Tensor:
+        """images: NCHW fp32 in [0,1] (encoded to x = 2*img-1 on the fly); returns NCHW fp32 model output."""
+        emb, h = self._embed_input(images, timesteps)
+        hs = []
         for layers in self.inp:
             h = self._run(layers, h, None, emb)
             hs.append(h)
         h = self._run(self.mid, h, None, emb)
         for layers in self.out:
             h = self._run(layers, h, hs.pop(), emb)
-        g, b = self.gn_out
-        ca, cb = ops.group_norm_coeffs(h, g, b, 32, dt)
-        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
-        co = out_channels or cfg.out_channels
-        out = torch.empty((n, co, hh, ww), dtype=torch.float32, device=dev)
-        call("pmi_finish_output", ptr(y), y.shape[-1], ptr(out), n, hh, ww, co)
-        return out
+        ca, cb = ops.group_norm_coeffs(h, *self.gn_out, 32, self.dt)
+        return self._output(h, ca, cb, out_channels)
 
     # ---- input gradient (SURVEY §8 row f2) -----------------------------------------------------------------------------------
     # Upstream GuidedDiffusion.predicted_noise is differentiable (guided_diffusion.py:125-133) and runs its blocks through CheckpointFunction
     # (nn.py:138-189, unet.py:228-229, 292): activations are dropped and recomputed in the backward to fit 16-40 GB cards.  Here the
     # training-mode forward keeps them instead -- every tensor it keeps is one the inference forward writes to HBM anyway (block inputs,
-    # conv1 outputs, attention operands), about 26 GB for GD "standard" at 512x512 x 8 of 288 GB -- and backward() walks the tape once: no
-    # recomputation.  dX of a convolution is the forward kernel on transposed + flipped weights (packed lazily); GroupNorm32 (+FiLM) + SiLU
-    # backward is pmi_gn_bwd_*; attention backward is the ViT's flash backward (64-channel heads) or batched GEMMs with the kept softmax.
+    # conv1 outputs, attention operands), 14.2 GB for GD "standard" at 512x512 x 8 of 288 GB (DESIGN.md §7) -- and backward() walks the tape
+    # once: no recomputation.  dX of a convolution is the forward kernel on transposed + flipped weights (ops.packed_dx); GroupNorm32 (+FiLM)
+    # + SiLU backward is pmi_gn_bwd_*; attention backward is ops.self_attention_backward.
     def _check_train(self):
         if self.precise:
             raise NotImplementedError("the ADM input gradient runs in the 16-bit modes (bf16 / f16)")
-
-    def _wt(self, key, weight, cin_pad=None):
-        """Packed weights of the input-gradient convolution of `weight` [Cout, Cin, k(, k)]: [Cin, Cout, k, k] with both taps flipped."""
-        if key not in self.w:
-            w = weight.detach().float()
-            if w.ndim == 3:
-                w = w[..., None]
-            w = w.permute(1, 0, 2, 3)
-            if w.shape[-1] == 3:
-                w = w.flip(2, 3)
-            self.w[key] = PackedLinear(w.contiguous(), None, self.dt, self.device, cin_pad=cin_pad)
-        return self.w[key]
 
     def _qkv_order1(self, l: _Attn, sd):
         """qkv projection producing channels (q|k|v, head, d) -- the layout of pmi_vit_attn_fwd / ops.attention_train -- whatever the
@@ -374,30 +368,16 @@ class AdmEngine:
     def _attn_train(self, l: _Attn, x, tape, sd):
         dt, w = self.dt, self.w
         n, hh, ww, c = x.shape
-        t, d = hh * ww, c // l.heads
+        t = hh * ww
         g, b = w[l.p + ".gn"]
         ca, cb, parts = ops.group_norm_coeffs_train(x, g, b, 32, dt)
         hn = torch.empty_like(x)
         call("pmi_gn_apply", ptr(x), None, c, ptr(ca), ptr(cb), None, ptr(hn), n, hh, ww, c, ACT_NONE, 0, dt)
         lin, _ = self._qkv_order1(l, sd)
-        qkv = ops.igemm(hn.view(n * t, c), lin)
-        if d == 64:                                  # flash-style forward keeping the log-sum-exp (csrc/attn.hip)
-            tp32 = (t + 31) // 32 * 32
-            aws = torch.empty((6, n * l.heads, tp32, 64), dtype=x.dtype, device=x.device)
-            lse = torch.empty((n * l.heads, tp32), dtype=torch.float32, device=x.device)
-            a = torch.empty((n * t, c), dtype=x.dtype, device=x.device)
-            call("pmi_vit_attn_fwd", ptr(qkv), ptr(aws), ptr(lse), ptr(a), n, t, l.heads, 64.0 ** -0.5, dt)
-            saved = (aws, lse, a)
-        else:                                        # other head dims (the tiny test configs): batched GEMMs, the softmax is kept
-            a, pm = ops.attention_train(qkv.view(n, t, 3 * c), l.heads, dt)
-            a = a.view(n * t, c)
-            saved = (qkv, pm)
+        a, saved = ops.self_attention_train(ops.igemm(hn.view(n * t, c), lin), n, t, l.heads, dt)
         out = ops.igemm(a, w[l.p + ".proj"], residual=x.view(n * t, c), want_stats=True, hw=t)
-        o4 = out.view(n, hh, ww, c)
-        if hasattr(out, "_pmi_stats"):
-            o4._pmi_stats = out._pmi_stats
         tape.append(("attn", l, x, (ca, cb, parts), saved))
-        return o4
+        return ops.view_nhwc(out, n, hh, ww)
 
     def _run_train(self, layers, h, h1, emb, tape, sd):
         for l in layers:
@@ -421,23 +401,10 @@ class AdmEngine:
     def forward_train(self, images: torch.Tensor, timesteps: torch.Tensor, state_dict, out_channels: Optional[int] = None):
         """As forward(), keeping what backward() needs.  Returns (model output NCHW fp32, tape)."""
         self._check_train()
-        cfg, dt, dev = self.cfg, self.dt, self.device
-        if not images.is_cuda:
-            raise RuntimeError("AdmEngine runs on a HIP device only (no CPU fallback)")
+        emb, h = self._embed_input(images, timesteps)
         sd = state_dict
-        images = images.float().contiguous()
-        n, _, hh, ww = images.shape
-        t = timesteps.to(device=dev, dtype=torch.float32).contiguous()
-        tdt = _hip.TORCH_DTYPE[dt]
-        temb = torch.empty((n, cfg.model_channels), dtype=tdt, device=dev)
-        call("pmi_timestep_embedding", ptr(t), ptr(temb), n, cfg.model_channels, 10000.0, dt)
-        e = ops.igemm(temb, self.te0, act=ACT_SILU)
-        e = ops.igemm(e, self.te2, act=ACT_SILU)
-        emb = ops.igemm(e, self.emb_all, out_f32=True)
-        x = torch.empty((n, hh, ww, 8), dtype=tdt, device=dev)
-        call("pmi_prep_input", ptr(images), None, 0, ptr(x), n, hh, ww, 8, dt)
         tape = {"inp": [], "mid": [], "out": []}
-        h, hs = x, []
+        hs = []
         for layers in self.inp:
             tp = []
             h = self._run_train(layers, h, None, emb, tp, sd)
@@ -448,68 +415,46 @@ class AdmEngine:
             tp = []
             h = self._run_train(layers, h, hs.pop(), emb, tp, sd)
             tape["out"].append(tp)
-        g, b = self.gn_out
-        ca, cb, parts = ops.group_norm_coeffs_train(h, g, b, 32, dt)
-        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
+        ca, cb, parts = ops.group_norm_coeffs_train(h, *self.gn_out, 32, self.dt)
         tape["last"] = (h, (ca, cb, parts))
         tape["emb_ld"] = emb.stride(0)
-        co = out_channels or cfg.out_channels
-        out = torch.empty((n, co, hh, ww), dtype=torch.float32, device=dev)
-        call("pmi_finish_output", ptr(y), y.shape[-1], ptr(out), n, hh, ww, co)
-        return out, tape
+        return self._output(h, ca, cb, out_channels), tape
 
     def _resample_bwd(self, l: _Res, g):
-        """Gradient through the block's resampling of a path: up -> sum of the 2x2 block, down -> a quarter to each of the 4 pixels."""
-        n, h, w_, c = g.shape
+        """Gradient through the block's resampling of a path (nearest x2 up / 2x2 average down)."""
         if l.up:
-            out = torch.empty((n, h // 2, w_ // 2, c), dtype=g.dtype, device=g.device)
-            call("pmi_upsample_nearest2_bwd", ptr(g), ptr(out), n, h // 2, w_ // 2, c, self.dt)
-            return out
-        if l.down:
-            out = torch.empty((n, 2 * h, 2 * w_, c), dtype=g.dtype, device=g.device)
-            call("pmi_avgpool2_bwd", ptr(g), ptr(out), n, 2 * h, 2 * w_, c, self.dt)
-            return out
-        return g
+            return ops.upsample_nearest2_bwd(g, self.dt)
+        return ops.avgpool2_bwd(g, self.dt) if l.down else g
 
     def _res_back(self, rec, g, sd, ld):
         _, l, x, x1, gn1, h, gn2, film = rec
-        dt, w = self.dt, self.w
+        dt, w, dev = self.dt, self.w, self.device
         p = l.p
-        d_a2 = ops.igemm(g, self._wt(p + ".conv2T", sd[p + ".out_layers.3.weight"]))            # wrt SiLU(GN2(h))
+        d_a2 = ops.igemm(g, ops.packed_dx(w, p + ".conv2T", sd[p + ".out_layers.3.weight"], dt, dev))                # wrt SiLU(GN2(h))
         dh, _ = ops.group_norm_backward(h, d_a2, gn2[0], gn2[1], gn2[2], w[p + ".gn2"][0], 32, dt, film=film, film_ld=ld if film is not None else 0,
                                         act=ACT_SILU)
-        d_a1 = self._resample_bwd(l, ops.igemm(dh, self._wt(p + ".conv1T", sd[p + ".in_layers.2.weight"])))     # wrt SiLU(GN1(cat(x, x1)))
+        d_a1 = self._resample_bwd(l, ops.igemm(dh, ops.packed_dx(w, p + ".conv1T", sd[p + ".in_layers.2.weight"], dt, dev)))   # wrt SiLU(GN1(cat(x, x1)))
         if l.cin != l.cout:
             skw = sd[p + ".skip_connection.weight"]
             if x1 is None:
-                gs0, gs1 = ops.igemm(g, self._wt(p + ".skipT", skw)), None
+                gs0, gs1 = ops.igemm(g, ops.packed_dx(w, p + ".skipT", skw, dt, dev)), None
             else:
                 c0 = x.shape[-1]
-                gs0 = ops.igemm(g, self._wt(p + ".skipT0", skw[:, :c0]))
-                gs1 = ops.igemm(g, self._wt(p + ".skipT1", skw[:, c0:]))
+                gs0 = ops.igemm(g, ops.packed_dx(w, p + ".skipT0", skw[:, :c0], dt, dev))
+                gs1 = ops.igemm(g, ops.packed_dx(w, p + ".skipT1", skw[:, c0:], dt, dev))
         else:
             gs0, gs1 = self._resample_bwd(l, g), None
         return ops.group_norm_backward(x, d_a1, gn1[0], gn1[1], gn1[2], w[p + ".gn1"][0], 32, dt, x1=x1, act=ACT_SILU, gadd0=gs0, gadd1=gs1)
 
     def _attn_back(self, rec, g, sd):
         _, l, x, gn, saved = rec
-        dt, w = self.dt, self.w
+        dt, w, dev = self.dt, self.w, self.device
         n, hh, ww, c = x.shape
-        t, d = hh * ww, c // l.heads
-        g2 = g.reshape(n * t, c)
-        da = ops.igemm(g2, self._wt(l.p + ".projT", sd[l.p + ".proj_out.weight"]))
-        if d == 64:
-            aws, lse, a = saved
-            tp32 = (t + 31) // 32 * 32
-            bws = torch.empty((2, n * l.heads, tp32, 64), dtype=x.dtype, device=x.device)
-            delta = torch.empty((n * l.heads, tp32), dtype=torch.float32, device=x.device)
-            dqkv = torch.empty((n * t, 3 * c), dtype=x.dtype, device=x.device)
-            call("pmi_vit_attn_bwd", ptr(aws), ptr(lse), ptr(a), ptr(da), ptr(bws), ptr(delta), ptr(dqkv), n, t, l.heads, 64.0 ** -0.5, dt)
-        else:
-            qkv, pm = saved
-            dqkv = ops.attention_backward(qkv.view(n, t, 3 * c), pm, da.view(n, t, c), l.heads, dt).view(n * t, 3 * c)
+        t = hh * ww
+        da = ops.igemm(g.reshape(n * t, c), ops.packed_dx(w, l.p + ".projT", sd[l.p + ".proj_out.weight"], dt, dev))
+        dqkv = ops.self_attention_backward(saved, da, n, t, l.heads, dt)
         _, wq = self._qkv_order1(l, sd)
-        dhn = ops.igemm(dqkv, self._wt(l.p + ".qkvT", wq)).view(n, hh, ww, c)
+        dhn = ops.igemm(dqkv, ops.packed_dx(w, l.p + ".qkvT", wq, dt, dev)).view(n, hh, ww, c)
         gx, _ = ops.group_norm_backward(x, dhn, gn[0], gn[1], gn[2], w[l.p + ".gn"][0], 32, dt, act=ACT_NONE, gadd0=g.contiguous())
         return gx
 
@@ -524,40 +469,30 @@ class AdmEngine:
                 g = self._attn_back(rec, g, sd)
             elif rec[0] == "resample":
                 l = rec[1]
-                wt = self._wt(l.p + "T", sd[l.p + (".conv" if l.up else ".op") + ".weight"])
+                wt = ops.packed_dx(self.w, l.p + "T", sd[l.p + (".conv" if l.up else ".op") + ".weight"], self.dt, self.device)
                 if l.up:                             # conv over nearest-up(x): dX at the high resolution, then the sum of each 2x2 block
-                    d = ops.igemm(g, wt)
-                    n, h_, w_, c = d.shape
-                    g = torch.empty((n, h_ // 2, w_ // 2, c), dtype=d.dtype, device=d.device)
-                    call("pmi_upsample_nearest2_bwd", ptr(d), ptr(g), n, h_ // 2, w_ // 2, c, self.dt)
+                    g = ops.upsample_nearest2_bwd(ops.igemm(g, wt), self.dt)
                 else:                                # stride-2 conv: dX = stride-1 conv of the zero-inserted gradient with the flipped weights
                     n, h_, w_, c = g.shape           # (two torch ops for the layout step: only the conv_resample configs -- pixelart -- come here)
                     z = torch.zeros((n, 2 * h_, 2 * w_, c), dtype=g.dtype, device=g.device)
                     z[:, ::2, ::2] = g
                     g = ops.igemm(z, wt)
             else:                                    # the first convolution: fp32 gradient wrt the padded input
-                g = ops.igemm(g, self._wt(rec[1][1] + "T", sd[rec[1][1] + ".weight"]), out_f32=True)
+                g = ops.igemm(g, ops.packed_dx(self.w, rec[1][1] + "T", sd[rec[1][1] + ".weight"], self.dt, self.device), out_f32=True)
         return g, g1
 
     @torch.no_grad()
     def backward(self, tape, d_out: torch.Tensor, state_dict) -> torch.Tensor:
         """d loss / d images (NCHW fp32, images in [0, 1]) from d loss / d output (NCHW fp32, the first d_out.shape[1] output channels) and the
-        tape of forward_train().  f16 engines scale the gradient by a power of two on the way in and back on the way out (image gradients
-        of a CLIP loss are ~1e-6 and would flush to zero in f16); bf16 needs no scaling."""
+        tape of forward_train().  f16 engines scale the gradient by a power of two on the way in and back on the way out
+        (ops.grad_to_nhwc); bf16 needs no scaling."""
         self._check_train()
-        dev, dt = self.device, self.dt
-        n, co, hh, ww = d_out.shape
+        dt = self.dt
         sd = {k: v.detach() for k, v in state_dict.items()}
-        scale = 1.0
-        if dt == _hip.DT_F16:
-            amax = float(d_out.abs().max())
-            if amax > 0.0 and amax == amax:
-                scale = 2.0 ** max(-24, min(24, -int(torch.tensor(amax).log2().ceil())))
-        g = torch.zeros((n, hh, ww, 8), dtype=_hip.TORCH_DTYPE[dt], device=dev)                # output channels + padding (layout only)
-        g[..., :co] = (d_out.to(dev).float() * scale).permute(0, 2, 3, 1)
+        g, scale = ops.grad_to_nhwc(d_out, dt, self.device)                                     # output channels + padding
         ld = tape["emb_ld"]
         h, gn = tape["last"]
-        d_act = ops.igemm(g, self._wt("out.2T", sd["out.2.weight"], cin_pad=8))
+        d_act = ops.igemm(g, ops.packed_dx(self.w, "out.2T", sd["out.2.weight"], self.dt, self.device, cin_pad=8))
         g, _ = ops.group_norm_backward(h, d_act, gn[0], gn[1], gn[2], self.gn_out[0], 32, dt, act=ACT_SILU)
         g_hs = []                                                                               # gradients of the skip tensors, in pop order
         for tp in reversed(tape["out"]):
@@ -570,6 +505,4 @@ class AdmEngine:
             tot = torch.empty_like(g)
             call("pmi_add16", ptr(g), ptr(gk), ptr(tot), g.numel(), dt)                         # hs[i] feeds the next block AND an out block
             g, _ = self._back(tape["inp"][i], tot, sd, ld)
-        out = torch.empty((n, 3, hh, ww), dtype=torch.float32, device=dev)
-        call("pmi_finish_output", ptr(g), g.shape[-1], ptr(out), n, hh, ww, 3)
-        return out * (2.0 / scale)                                                              # x = 2 * images - 1
+        return ops.grad_to_nchw(g, 3, 2.0 / scale)                                              # x = 2 * images - 1

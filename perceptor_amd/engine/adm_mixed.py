@@ -23,12 +23,12 @@ Kernels: csrc/conv_wd.hip (SIN = 1 / 2 staging, split epilogue with statistics),
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict
 
 import torch
 
 from .. import _hip
-from .._hip import ACT_SILU, DT_F16, DT_F16X2, call, ptr
+from .._hip import ACT_SILU, DT_F16, DT_F16X2
 from . import ops
 from .adm import AdmConfig, AdmEngine, _Attn, _Res, _Resample, build_plan  # noqa: F401
 from .ops import MixedLinear, PackedLinear
@@ -205,34 +205,3 @@ class AdmMixedEngine(AdmEngine):
                     self.dt = DT_F16X2
             h1 = None
         return h
-
-    @torch.no_grad()
-    def forward(self, images: torch.Tensor, timesteps: torch.Tensor, out_channels: Optional[int] = None) -> torch.Tensor:
-        """images: NCHW fp32 in [0,1] (encoded to x = 2*img-1 on the fly); returns NCHW fp32 model output."""
-        cfg, dev = self.cfg, self.device
-        if not images.is_cuda:
-            raise RuntimeError("AdmMixedEngine runs on a HIP device only (no CPU fallback)")
-        images = images.float().contiguous()
-        n, _, hh, ww = images.shape
-        t = timesteps.to(device=dev, dtype=torch.float32).contiguous()
-        temb = torch.empty((n, cfg.model_channels), dtype=torch.float32, device=dev)
-        call("pmi_timestep_embedding", ptr(t), ptr(temb), n, cfg.model_channels, 10000.0, DT_F16X2)
-        e = ops.linear_f32(temb, *self.te0, act=ACT_SILU)
-        e = ops.linear_f32(e, *self.te2, act=ACT_SILU)
-        emb = ops.linear_f32(e, *self.emb_all)
-        x = torch.empty((n, hh, ww, 16), dtype=torch.float16, device=dev)
-        call("pmi_prep_input", ptr(images), None, 0, ptr(x), n, hh, ww, 8, DT_F16X2)
-        h, hs = x, []
-        for layers in self.inp:
-            h = self._run(layers, h, None, emb)
-            hs.append(h)
-        h = self._run(self.mid, h, None, emb)
-        for layers in self.out:
-            h = self._run(layers, h, hs.pop(), emb)
-        g, b = self.gn_out
-        ca, cb = ops.group_norm_coeffs(h, g, b, 32, DT_F16X2)
-        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
-        co = out_channels or cfg.out_channels
-        out = torch.empty((n, co, hh, ww), dtype=torch.float32, device=dev)
-        call("pmi_finish_output", ptr(y), y.shape[-1], ptr(out), n, hh, ww, co)
-        return out

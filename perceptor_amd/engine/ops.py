@@ -6,6 +6,7 @@ used only for device memory.
 """
 from __future__ import annotations
 
+import math
 import os
 import ctypes as C
 from typing import Optional
@@ -200,6 +201,66 @@ class MixedLinear:
             w, b, dev, src, cp = self._args
             self._dbl = PackedLinear(w, b, DT_F16X2, dev, cin_pad=cp, sources=src)
         return self._dbl
+
+
+# ---- input gradients: dX of a convolution is the forward kernel on transposed + flipped weights -------------------------------------
+def packed_dx(cache: dict, key: str, weight: torch.Tensor, dt: int, device, cin_pad: Optional[int] = None,
+              rows: Optional[int] = None) -> PackedLinear:
+    """Packed weights of the input-gradient convolution of `weight` ([Cout, Cin] linear, [Cout, Cin, 1] Conv1d or [Cout, Cin, k, k]):
+    [Cin, Cout, k, k] with both taps flipped, built once and kept in cache[key].  rows: zero-pad its output channels (the forward's
+    zero-padded input channels) to this count."""
+    if key not in cache:
+        wt = weight.detach().cpu().float()
+        if wt.ndim == 3:
+            wt = wt[..., None]
+        elif wt.ndim == 2:
+            wt = wt[:, :, None, None]
+        wt = wt.permute(1, 0, 2, 3).flip(2, 3)
+        if rows is not None and rows > wt.shape[0]:
+            wt = torch.cat([wt, wt.new_zeros((rows - wt.shape[0],) + tuple(wt.shape[1:]))], 0)
+        cache[key] = PackedLinear(wt.contiguous(), None, dt, device, cin_pad=cin_pad)
+    return cache[key]
+
+
+def f16_grad_scale(amax) -> float:
+    """Power of two that keeps an f16 gradient in range, from the per-sample max |d_out|: 2**clamp(-ceil(log2(max)), -24, 24) in float64
+    (the largest value lands in (0.5, 1]; a power of two is exact), 1.0 when every sample is zero or any holds a NaN or an inf."""
+    amax = [float(a) for a in amax]
+    m = max(amax, default=0.0)
+    if not all(math.isfinite(a) for a in amax) or m <= 0.0:
+        return 1.0
+    return 2.0 ** max(-24, min(24, -math.ceil(math.log2(m))))
+
+
+def grad_to_nhwc(d_out: torch.Tensor, dt: int, device, cpad: int = 8, mul: float = 1.0):
+    """d loss / d output (NCHW fp32, any device) -> (NHWC 16-bit [N, H, W, cpad] = d_out * mul * scale, scale).  f16 scales by
+    f16_grad_scale (image gradients of a CLIP loss are ~1e-6 and would flush to zero in f16); bf16 needs no scaling."""
+    d = d_out.to(device=device, dtype=torch.float32).contiguous()
+    n, c, h, w = d.shape
+    scale = 1.0
+    if dt == _hip.DT_F16:
+        amax = _empty((n,), torch.float32, device)
+        call("pmi_quantile_abs", ptr(d), ptr(amax), n, c * h * w, 1.0)
+        scale = f16_grad_scale(amax.tolist())
+    g = _empty((n, h, w, cpad), _hip.TORCH_DTYPE[dt], device)
+    call("pmi_nchw_to_nhwc", ptr(d), ptr(g), n, c, h, w, cpad, mul * scale, 0.0, dt)
+    return g, scale
+
+
+def grad_to_nchw(g: torch.Tensor, c: int, mul: float) -> torch.Tensor:
+    """The first c channels of an fp32 NHWC gradient [N, H, W, >= c] as NCHW fp32, times mul (undoing the input scale)."""
+    n, h, w, _ = g.shape
+    out = _empty((n, c, h, w), torch.float32, g.device)
+    call("pmi_nhwc_to_nchw", ptr(g), g.shape[-1], ptr(out), n, h, w, c, mul, 0.0)
+    return out
+
+
+def view_nhwc(y: torch.Tensor, n: int, h: int, w: int) -> torch.Tensor:
+    """[N*H*W, C] as [N, H, W, C], keeping the GroupNorm statistics its producer left behind (_pmi_stats)."""
+    v = y.view(n, h, w, y.shape[-1])
+    if hasattr(y, "_pmi_stats"):
+        v._pmi_stats = y._pmi_stats
+    return v
 
 
 def split_convert(x: torch.Tensor, to_split: bool) -> torch.Tensor:
@@ -603,6 +664,31 @@ def upsample_nearest2(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def avgpool2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
+    """Adjoint of avgpool2: a quarter of each gradient value to each pixel of its 2x2 block, [N, H, W, C] -> [N, 2H, 2W, C]."""
+    n, h, w, c = g.shape
+    out = _empty((n, 2 * h, 2 * w, c), g.dtype, g.device)
+    call("pmi_avgpool2_bwd", ptr(g), ptr(out), n, 2 * h, 2 * w, c, dt)
+    return out
+
+
+def _up2_bwd(fn: str, g: torch.Tensor, dt: int) -> torch.Tensor:
+    n, h, w, c = g.shape
+    out = _empty((n, h // 2, w // 2, c), g.dtype, g.device)
+    call(fn, ptr(g), ptr(out), n, h // 2, w // 2, c, dt)
+    return out
+
+
+def upsample_nearest2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
+    """Adjoint of upsample_nearest2: the sum of each 2x2 block, [N, 2H, 2W, C] -> [N, H, W, C]."""
+    return _up2_bwd("pmi_upsample_nearest2_bwd", g, dt)
+
+
+def upsample_bilinear2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
+    """Adjoint of upsample_bilinear2, [N, 2H, 2W, C] -> [N, H, W, C]."""
+    return _up2_bwd("pmi_upsample_bilinear2_bwd", g, dt)
+
+
 def attention(qkv: torch.Tensor, heads: int, order: int, dt: int, causal: bool = False) -> torch.Tensor:
     """Self-attention over tokens.  qkv: [N, T, 3C] 16-bit -> [N, T, C].
     causal: query i sees keys 0..i (the CLIP text tower's mask, ruclip/model.py:181-185); runs the batched-GEMM path.
@@ -742,6 +828,36 @@ def attention_backward(qkv: torch.Tensor, p: torch.Tensor, d_out: torch.Tensor, 
     bgemm(dst, qt, dqkv, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=c3, batch=n * heads, batch_inner=heads,
           sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * c3, d), dt=dt, d_off=c)            # dK
     return dqkv
+
+
+def self_attention_train(qkv: torch.Tensor, n: int, t: int, heads: int, dt: int):
+    """Self-attention keeping what self_attention_backward needs: qkv [N*T, 3C] 16-bit, channels (q|k|v, head, d) -> (out [N*T, C], saved).
+    64-channel heads run the flash-style forward that keeps the log-sum-exp (csrc/attn.hip), other head dims attention_train."""
+    c = qkv.shape[-1] // 3
+    if c // heads == 64:
+        tp32 = (t + 31) // 32 * 32
+        aws = _empty((6, n * heads, tp32, 64), qkv.dtype, qkv.device)
+        lse = _empty((n * heads, tp32), torch.float32, qkv.device)
+        a = _empty((n * t, c), qkv.dtype, qkv.device)
+        call("pmi_vit_attn_fwd", ptr(qkv), ptr(aws), ptr(lse), ptr(a), n, t, heads, 64.0 ** -0.5, dt)
+        return a, (aws, lse, a)
+    a, pm = attention_train(qkv.view(n, t, 3 * c), heads, dt)
+    return a.view(n * t, c), (qkv, pm)
+
+
+def self_attention_backward(saved, da: torch.Tensor, n: int, t: int, heads: int, dt: int) -> torch.Tensor:
+    """d loss / d qkv [N*T, 3C] from d loss / d out [N*T, C] and self_attention_train's `saved`."""
+    c = da.shape[-1]
+    if c // heads == 64:
+        aws, lse, a = saved
+        tp32 = (t + 31) // 32 * 32
+        bws = _empty((2, n * heads, tp32, 64), da.dtype, da.device)
+        delta = _empty((n * heads, tp32), torch.float32, da.device)
+        dqkv = _empty((n * t, 3 * c), da.dtype, da.device)
+        call("pmi_vit_attn_bwd", ptr(aws), ptr(lse), ptr(a), ptr(da), ptr(bws), ptr(delta), ptr(dqkv), n, t, heads, 64.0 ** -0.5, dt)
+        return dqkv
+    qkv, pm = saved
+    return attention_backward(qkv.view(n, t, 3 * c), pm, da.view(n, t, c), heads, dt).view(n * t, 3 * c)
 
 
 def gemm_f32(A: torch.Tensor, B: torch.Tensor, D: torch.Tensor, *, M: int, N: int, K: int, lda: int, ldb: int, ldd: int, trans_b: bool = False,

@@ -156,12 +156,6 @@ class ResNetEngine:
         call("pmi_act_bwd", ptr(g), ptr(y), ptr(out), g.numel(), ACT_RELU, self.dt)
         return out
 
-    def _pool_bwd(self, g):
-        n, h, w, c = g.shape
-        out = torch.empty((n, 2 * h, 2 * w, c), dtype=g.dtype, device=g.device)
-        call("pmi_avgpool2_bwd", ptr(g), ptr(out), n, 2 * h, 2 * w, c, self.dt)
-        return out
-
     # ---- forward --------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, images: torch.Tensor, save: bool = False):
@@ -238,18 +232,18 @@ class ResNetEngine:
             gy = self._relu_bwd(g, y)
             gh = ops.igemm(gy, blk["c3"].bwd)
             if blk["stride"] > 1:
-                gh = self._pool_bwd(gh)
+                gh = ops.avgpool2_bwd(gh, self.dt)
             gh = self._relu_bwd(gh, h2)
             gh = self._relu_bwd(ops.igemm(gh, blk["c2"].bwd), h1)
             if blk["ds"] is not None:
                 gs = ops.igemm(gy, blk["ds"].bwd)
                 if blk["stride"] > 1:
-                    gs = self._pool_bwd(gs)
+                    gs = ops.avgpool2_bwd(gs, self.dt)
             else:
                 gs = gy
             g = ops.igemm(gh, blk["c1"].bwd, residual=gs)                        # conv1's dX + the skip path's gradient in one epilogue
         s1, s2, s3 = sv["stem"]
-        g = self._relu_bwd(self._pool_bwd(g), s3)
+        g = self._relu_bwd(ops.avgpool2_bwd(g, self.dt), s3)
         g = self._relu_bwd(ops.igemm(g, self.stem[2].bwd), s2)
         g = self._relu_bwd(ops.igemm(g, self.stem[1].bwd), s1)
         nb, h_, w_, cg = g.shape             # stride-2 convolution: dX = stride-1 convolution of the zero-inserted gradient, flipped weights

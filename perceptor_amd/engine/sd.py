@@ -19,7 +19,6 @@ so a real checkpoint's tensors load as they are.
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -303,10 +302,7 @@ class _Blocks:
         qkv = ops.igemm(hn.view(m, cc), w[a + ".qkv"])
         at = ops.attention(qkv.view(n, h2 * w2, 3 * cc), 1, 1, dt)
         o = ops.igemm(at.view(m, cc), w[a + ".proj"], residual=h.view(m, cc), want_stats=True, hw=h2 * w2)
-        h4 = o.view(n, h2, w2, cc)
-        if hasattr(o, "_pmi_stats"):
-            h4._pmi_stats = o._pmi_stats
-        return h4
+        return ops.view_nhwc(o, n, h2, w2)
 
 
 class SdUnetEngine(_Blocks):
@@ -385,10 +381,7 @@ class SdUnetEngine(_Blocks):
         gg = ops.geglu_linear(self._ln(h, w[b + ".norm3"], m, c), w[b + ".ff1"])                  # value * gelu(gate), [m, 4c]
         h16 = ops.igemm(gg, w[b + ".ff2"], residual=h)                                            # fp32 residual in, 16-bit tokens out
         out = ops.igemm(h16, w[k + ".proj_out"], residual=x.view(m, c), want_stats=True, hw=t)
-        o4 = out.view(n, hh, ww, c)
-        if hasattr(out, "_pmi_stats"):
-            o4._pmi_stats = out._pmi_stats
-        return o4
+        return ops.view_nhwc(out, n, hh, ww)
 
     def _run(self, blk, h, h1, emb, kv_all, tc):
         for l in blk:
@@ -472,21 +465,33 @@ class VaeDecoderEngine(_Blocks):
         self.conv_out = self._lin("decoder.conv_out")
         self.sd = None
 
-    @torch.no_grad()
-    def forward(self, latents: torch.Tensor, scale: float = 1.0 / 0.18215, to_images: bool = True) -> torch.Tensor:
-        """latents NCHW fp32 (the UNet's space) -> images NCHW fp32 in [0, 1] (to_images) or the decoder's x in [-1, 1]."""
-        cfg, dt, dev, w = self.cfg, self.dt, self.device, self.w
+    def _conv_in(self, latents, scale):
+        """latents NCHW fp32 -> latents * scale as NHWC 16-bit -> post_quant_conv -> conv_in (with its GroupNorm statistics)."""
+        cfg, dt = self.cfg, self.dt
         if not latents.is_cuda:
             raise RuntimeError("VaeDecoderEngine runs on a HIP device only (no CPU fallback)")
         latents = latents.float().contiguous()
         n, c, hh, ww = latents.shape
         if c != cfg.latent_channels:
             raise ValueError(f"latents must have {cfg.latent_channels} channels")
-        tdt = _hip.TORCH_DTYPE[dt]
-        x = torch.empty((n, hh, ww, self.pq.cin_p), dtype=tdt, device=dev)
+        x = torch.empty((n, hh, ww, self.pq.cin_p), dtype=_hip.TORCH_DTYPE[dt], device=self.device)
         call("pmi_nchw_to_nhwc", ptr(latents), ptr(x), n, c, hh, ww, self.pq.cin_p, float(scale), 0.0, dt)
-        z = ops.igemm(x, self.pq)
-        h = ops.igemm(z, self.conv_in, want_stats=True)
+        return ops.igemm(ops.igemm(x, self.pq), self.conv_in, want_stats=True)
+
+    def _output(self, h, ca, cb, to_images):
+        """conv_out on SiLU(GroupNorm(h)) given the norm's coefficients -> NCHW fp32 images in [0, 1] (to_images) or x in [-1, 1]."""
+        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
+        n, ho, wo, _ = y.shape
+        out = torch.empty((n, self.cfg.out_channels, ho, wo), dtype=torch.float32, device=self.device)
+        mul, add = (0.5, 0.5) if to_images else (1.0, 0.0)          # diffusion_space.decode: (x + 1) / 2
+        call("pmi_nhwc_to_nchw", ptr(y), y.shape[-1], ptr(out), n, ho, wo, self.cfg.out_channels, mul, add)
+        return out
+
+    @torch.no_grad()
+    def forward(self, latents: torch.Tensor, scale: float = 1.0 / 0.18215, to_images: bool = True) -> torch.Tensor:
+        """latents NCHW fp32 (the UNet's space) -> images NCHW fp32 in [0, 1] (to_images) or the decoder's x in [-1, 1]."""
+        cfg, dt, w = self.cfg, self.dt, self.w
+        h = self._conv_in(latents, scale)
         g, eps = cfg.groups, 1e-6
         h = self._resnet("decoder.mid_block.resnets.0", h, None, None, g, eps)
         h4 = self._vae_attention("decoder.mid_block.attentions.0", h, g)
@@ -494,12 +499,7 @@ class VaeDecoderEngine(_Blocks):
         for kind, k in self.plan:
             h = self._resnet(k, h, None, None, g, eps) if kind == "res" else ops.igemm(h, w[k], up=True, want_stats=True)
         ca, cb = ops.group_norm_coeffs(h, *self.gn_out, g, dt, eps=eps)
-        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
-        _, ho, wo, _ = y.shape
-        out = torch.empty((n, cfg.out_channels, ho, wo), dtype=torch.float32, device=dev)
-        mul, add = (0.5, 0.5) if to_images else (1.0, 0.0)          # diffusion_space.decode: (x + 1) / 2
-        call("pmi_nhwc_to_nchw", ptr(y), y.shape[-1], ptr(out), n, ho, wo, cfg.out_channels, mul, add)
-        return out
+        return self._output(h, ca, cb, to_images)
 
     # ---- input gradient (d loss / d latents through the frozen decoder: loss-guided sampling) -----------------------------------------
     # forward_train() issues forward()'s launch sequence and keeps the operands of every nonlinear step: per ResnetBlock2D its input x,
@@ -528,27 +528,14 @@ class VaeDecoderEngine(_Blocks):
         at, pm = ops.attention_train(qkv.view(n, h2 * w2, 3 * cc), 1, dt)       # = ops.attention's batched-GEMM path (head dim > 160)
         o = ops.igemm(at.view(m, cc), w[a + ".proj"], residual=x.view(m, cc), want_stats=True, hw=h2 * w2)
         tape.append(("attn", a, x, (ca, cb, parts), qkv, pm))
-        h4 = o.view(n, h2, w2, cc)
-        if hasattr(o, "_pmi_stats"):
-            h4._pmi_stats = o._pmi_stats
-        return h4
+        return ops.view_nhwc(o, n, h2, w2)
 
     @torch.no_grad()
     def forward_train(self, latents: torch.Tensor, scale: float = 1.0 / 0.18215, to_images: bool = True):
         """As forward(), keeping what backward() needs: (images NCHW fp32, tape).  For head dims above 160 (SD-v1: 512) the value equals
         forward()'s bit for bit; a 64-channel head runs forward()'s d64 kernel there and the batched GEMMs here (rounding-level)."""
-        cfg, dt, dev, w = self.cfg, self.dt, self.device, self.w
-        if not latents.is_cuda:
-            raise RuntimeError("VaeDecoderEngine runs on a HIP device only (no CPU fallback)")
-        latents = latents.float().contiguous()
-        n, c, hh, ww = latents.shape
-        if c != cfg.latent_channels:
-            raise ValueError(f"latents must have {cfg.latent_channels} channels")
-        tdt = _hip.TORCH_DTYPE[dt]
-        x = torch.empty((n, hh, ww, self.pq.cin_p), dtype=tdt, device=dev)
-        call("pmi_nchw_to_nhwc", ptr(latents), ptr(x), n, c, hh, ww, self.pq.cin_p, float(scale), 0.0, dt)
-        z = ops.igemm(x, self.pq)
-        h = ops.igemm(z, self.conv_in, want_stats=True)
+        cfg, dt, w = self.cfg, self.dt, self.w
+        h = self._conv_in(latents, scale)
         g, eps = cfg.groups, 1e-6
         rec: List[tuple] = []
         h = self._resnet_train("decoder.mid_block.resnets.0", h, rec, g, eps)
@@ -561,61 +548,38 @@ class VaeDecoderEngine(_Blocks):
                 rec.append(("up", k))
                 h = ops.igemm(h, w[k], up=True, want_stats=True)
         ca, cb, parts = ops.group_norm_coeffs_train(h, *self.gn_out, g, dt, eps=eps)
-        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
-        _, ho, wo, _ = y.shape
-        out = torch.empty((n, cfg.out_channels, ho, wo), dtype=torch.float32, device=dev)
-        mul, add = (0.5, 0.5) if to_images else (1.0, 0.0)
-        call("pmi_nhwc_to_nchw", ptr(y), y.shape[-1], ptr(out), n, ho, wo, cfg.out_channels, mul, add)
+        out = self._output(h, ca, cb, to_images)
         tape = {"rec": rec, "last": (h, (ca, cb, parts)), "scale": float(scale), "to_images": bool(to_images),
-                "in_shape": (n, c, hh, ww), "out_shape": (n, cfg.out_channels, ho, wo)}
+                "in_shape": tuple(latents.shape), "out_shape": tuple(out.shape)}
         return out, tape
 
-    def _wt(self, key, weight, cin_pad=None, rows=None):
-        """Packed weights of the input-gradient convolution of `weight` [Cout, Cin(, k, k)] ([Cout, Cin] linears): [Cin, Cout, k, k] with
-        both taps flipped; rows: zero-pad its output channels (the forward's zero-padded input channels) to this count."""
-        if key not in self.w:
-            wt = weight.detach().cpu().float()
-            if wt.ndim == 2:
-                wt = wt[:, :, None, None]
-            wt = wt.permute(1, 0, 2, 3).flip(2, 3)
-            if rows is not None and rows > wt.shape[0]:
-                wt = torch.cat([wt, wt.new_zeros((rows - wt.shape[0],) + tuple(wt.shape[1:]))], 0)
-            self.w[key] = PackedLinear(wt.contiguous(), None, self.dt, self.device, cin_pad=cin_pad)
-        return self.w[key]
-
-    def _up_back(self, k, g, sd, fused: bool = True):
-        """Gradient wrt the input of nearest-x2 + conv3x3 from g = gradient wrt its output [N, 2h, 2w, C].  The folded one-pass kernel is
-        the faster one at all three SD-v1 shapes; fused=False runs the composed adjoint for the A/B of the probe."""
-        n, h2, w2, c = g.shape
-        if fused:
-            if k + ".fold" not in self.w:
-                self.w[k + ".fold"] = PackedLinear(fold_upsample_weights(sd[k + ".weight"].cpu()).float(), None, self.dt, self.device)
-            return ops.igemm(g, self.w[k + ".fold"], stride=2)
-        d = ops.igemm(g, self._wt(k + "T", sd[k + ".weight"]))
-        out = torch.empty((n, h2 // 2, w2 // 2, d.shape[-1]), dtype=d.dtype, device=d.device)
-        call("pmi_upsample_nearest2_bwd", ptr(d), ptr(out), n, h2 // 2, w2 // 2, d.shape[-1], self.dt)
-        return out
+    def _up_back(self, k, g, sd):
+        """Gradient wrt the input of nearest-x2 + conv3x3 from g = gradient wrt its output [N, 2h, 2w, C]: one stride-2 pass on the
+        phase-folded weights, faster at all three SD-v1 shapes than dX at the high resolution + the 2x2 sum."""
+        if k + ".fold" not in self.w:
+            self.w[k + ".fold"] = PackedLinear(fold_upsample_weights(sd[k + ".weight"].cpu()).float(), None, self.dt, self.device)
+        return ops.igemm(g, self.w[k + ".fold"], stride=2)
 
     def _res_back(self, rec, g, sd, groups, eps):
         _, k, x, gn1, h, gn2 = rec
-        dt, w = self.dt, self.w
-        d_a2 = ops.igemm(g, self._wt(k + ".conv2T", sd[k + ".conv2.weight"]))                  # wrt SiLU(GN2(h))
+        dt, w, dev = self.dt, self.w, self.device
+        d_a2 = ops.igemm(g, ops.packed_dx(w, k + ".conv2T", sd[k + ".conv2.weight"], dt, dev))                  # wrt SiLU(GN2(h))
         dh, _ = ops.group_norm_backward(h, d_a2, *gn2, w[k + ".gn2"][0], groups, dt, act=ACT_SILU, eps=eps)
-        d_a1 = ops.igemm(dh, self._wt(k + ".conv1T", sd[k + ".conv1.weight"]))                 # wrt SiLU(GN1(x))
-        gs = ops.igemm(g, self._wt(k + ".skipT", sd[k + ".conv_shortcut.weight"])) if (k + ".skip") in w else g
+        d_a1 = ops.igemm(dh, ops.packed_dx(w, k + ".conv1T", sd[k + ".conv1.weight"], dt, dev))                 # wrt SiLU(GN1(x))
+        gs = ops.igemm(g, ops.packed_dx(w, k + ".skipT", sd[k + ".conv_shortcut.weight"], dt, dev)) if (k + ".skip") in w else g
         gx, _ = ops.group_norm_backward(x, d_a1, *gn1, w[k + ".gn1"][0], groups, dt, act=ACT_SILU, gadd0=gs, eps=eps)
         return gx
 
     def _attn_back(self, rec, g, sd, groups):
         _, a, x, gn, qkv, pm = rec
-        dt, w = self.dt, self.w
+        dt, w, dev = self.dt, self.w, self.device
         n, h2, w2, cc = x.shape
         t, m = h2 * w2, n * h2 * w2
-        da = ops.igemm(g.view(m, cc), self._wt(a + ".projT", sd[a + ".proj_attn.weight"]))
+        da = ops.igemm(g.view(m, cc), ops.packed_dx(w, a + ".projT", sd[a + ".proj_attn.weight"], dt, dev))
         dqkv = ops.attention_backward(qkv.view(n, t, 3 * cc), pm, da.view(n, t, cc), 1, dt)
-        if a + ".qkvT" not in self.w:
-            self._wt(a + ".qkvT", torch.cat([sd[f"{a}.{nm}.weight"].cpu() for nm in ("query", "key", "value")], 0))
-        dhn = ops.igemm(dqkv.view(m, 3 * cc), self.w[a + ".qkvT"]).view(n, h2, w2, cc)
+        if a + ".qkvT" not in w:
+            ops.packed_dx(w, a + ".qkvT", torch.cat([sd[f"{a}.{nm}.weight"].cpu() for nm in ("query", "key", "value")], 0), dt, dev)
+        dhn = ops.igemm(dqkv.view(m, 3 * cc), w[a + ".qkvT"]).view(n, h2, w2, cc)
         gx, _ = ops.group_norm_backward(x, dhn, *gn, w[a + ".gn"][0], groups, dt, act=ACT_NONE, gadd0=g, eps=1e-6)
         return gx
 
@@ -624,28 +588,17 @@ class VaeDecoderEngine(_Blocks):
         """d loss / d latents (NCHW fp32) from d loss / d output (NCHW fp32, the shape forward_train() returned) and its tape.
         `state_dict`: the decoder's tensors by name (StableDiffusion.vae.state_dict()); the transposed / folded weights are packed from it on
         the first call and kept on the engine.  f16 engines scale the gradient by a power of two on the way in and back on the way out
-        (image gradients of a CLIP loss are ~1e-6 and would flush to zero in f16); bf16 needs no scaling."""
-        cfg, dt, dev = self.cfg, self.dt, self.device
+        (ops.grad_to_nhwc); bf16 needs no scaling."""
+        cfg, dt, dev, w = self.cfg, self.dt, self.device, self.w
         if not d_out.is_cuda:
             raise RuntimeError("VaeDecoderEngine runs on a HIP device only (no CPU fallback)")
         if tuple(d_out.shape) != tape["out_shape"]:
             raise ValueError(f"d_out must have the output's shape {tape['out_shape']}, got {tuple(d_out.shape)}")
-        d_out = d_out.float().contiguous()
-        n, co, ho, wo = tape["out_shape"]
         sd = state_dict
         g_, eps = cfg.groups, 1e-6
-        gscale = 1.0
-        if dt == _hip.DT_F16:
-            amax_n = torch.empty((n,), dtype=torch.float32, device=dev)
-            call("pmi_quantile_abs", ptr(d_out), ptr(amax_n), n, co * ho * wo, 1.0)           # per-sample max |d_out|
-            amax = max(amax_n.tolist())
-            if amax > 0.0 and amax == amax and amax != float("inf"):
-                gscale = 2.0 ** max(-24, min(24, -math.ceil(math.log2(amax))))
-        tdt = _hip.TORCH_DTYPE[dt]
-        g = torch.empty((n, ho, wo, 8), dtype=tdt, device=dev)
-        call("pmi_nchw_to_nhwc", ptr(d_out), ptr(g), n, co, ho, wo, 8, (0.5 if tape["to_images"] else 1.0) * gscale, 0.0, dt)
+        g, gscale = ops.grad_to_nhwc(d_out, dt, dev, mul=0.5 if tape["to_images"] else 1.0)
         h, gn = tape["last"]
-        d_act = ops.igemm(g, self._wt("decoder.conv_outT", sd["decoder.conv_out.weight"], cin_pad=8))
+        d_act = ops.igemm(g, ops.packed_dx(w, "decoder.conv_outT", sd["decoder.conv_out.weight"], dt, dev, cin_pad=8))
         g, _ = ops.group_norm_backward(h, d_act, *gn, self.gn_out[0], g_, dt, act=ACT_SILU, eps=eps)
         for rec in reversed(tape["rec"]):
             if rec[0] == "res":
@@ -655,16 +608,10 @@ class VaeDecoderEngine(_Blocks):
             else:
                 g = self._up_back(rec[1], g, sd)
         lp = self.pq.cin_p
-        gz = ops.igemm(g, self._wt("decoder.conv_inT", sd["decoder.conv_in.weight"], rows=lp))      # [.., lp]: rows past 4 are zero
-        if "post_quant_convT" not in self.w:                                                       # 1x1, 4 -> 4 padded to lp x lp
-            wq = torch.zeros((lp, lp))
-            wq[:cfg.latent_channels, :cfg.latent_channels] = sd["post_quant_conv.weight"].detach().cpu().float().flatten(1)
-            self._wt("post_quant_convT", wq)
-        gx = ops.igemm(gz, self.w["post_quant_convT"], out_f32=True)                               # [n, h, w, lp] fp32
-        _, c, hh, ww = tape["in_shape"]
-        out = torch.empty((n, c, hh, ww), dtype=torch.float32, device=dev)
-        call("pmi_nhwc_to_nchw", ptr(gx), gx.shape[-1], ptr(out), n, hh, ww, c, tape["scale"] / gscale, 0.0)
-        return out
+        gz = ops.igemm(g, ops.packed_dx(w, "decoder.conv_inT", sd["decoder.conv_in.weight"], dt, dev, rows=lp))   # [.., lp]: rows past 4 are 0
+        pqt = ops.packed_dx(w, "post_quant_convT", sd["post_quant_conv.weight"], dt, dev, rows=lp)                  # 1x1, 4 -> 4 padded to lp
+        gx = ops.igemm(gz, pqt, out_f32=True)                                                                      # [n, h, w, lp] fp32
+        return ops.grad_to_nchw(gx, cfg.latent_channels, tape["scale"] / gscale)
 
 
 class VaeEncoderEngine(_Blocks):

@@ -163,7 +163,7 @@ class VDiffEngine:
         f32 = lambda k: sd[k].detach().float().to(dev).contiguous()
         self.w: Dict[str, object] = {}
         mods, off, mod_keys = [], [0], []
-        self._mod_keys, self._dmod = mod_keys, None
+        self._mod_keys = mod_keys
         first = [True]
 
         def pack(l, p):
@@ -284,9 +284,9 @@ class VDiffEngine:
         cond = ops.igemm(h, m["b2"], residual=z1)
         return ops.igemm(cond, self.mod_all, out_f32=True)           # every Modulation2d's (scale|shift) at once
 
-    @torch.no_grad()
-    def forward(self, images: torch.Tensor, t: torch.Tensor, clip_embed: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """images NCHW fp32 in [0,1]; t [N] float in (0,1]; returns v, NCHW fp32 [N,3,H,W]."""
+    def _embed_input(self, images, t, clip_embed):
+        """Mapping network (conditioned nets: every Modulation2d's scale | shift, or None), Fourier planes of t and the padded NHWC input
+        x = cat(2 * images - 1, planes): (mod, x)."""
         if not images.is_cuda:
             raise RuntimeError("VDiffEngine runs on a HIP device only (no CPU fallback)")
         dt, dev = self.dt, self.device
@@ -305,8 +305,18 @@ class VDiffEngine:
         call("pmi_fourier_features", ptr(tf), ptr(self.tw), ptr(planes), n, 8)
         x = torch.empty((n, hh, ww, 48 if self.precise else 24), dtype=_hip.TORCH_DTYPE[dt], device=dev)
         call("pmi_prep_input", ptr(images), ptr(planes), 16, ptr(x), n, hh, ww, 24, dt)
-        y = self._run(self.spec["net"], "net", x, mod)
-        out = torch.empty((n, 3, hh, ww), dtype=torch.float32, device=dev)
+        return mod, x
+
+    @torch.no_grad()
+    def forward(self, images: torch.Tensor, t: torch.Tensor, clip_embed: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """images NCHW fp32 in [0,1]; t [N] float in (0,1]; returns v, NCHW fp32 [N,3,H,W]."""
+        mod, x = self._embed_input(images, t, clip_embed)
+        return self._output(self._run(self.spec["net"], "net", x, mod))
+
+    def _output(self, y):
+        """The net's NHWC fp32 output (3 channels + padding) as NCHW fp32 v."""
+        n, hh, ww, _ = y.shape
+        out = torch.empty((n, 3, hh, ww), dtype=torch.float32, device=self.device)
         call("pmi_finish_output", ptr(y), y.shape[-1], ptr(out), n, hh, ww, 3)
         return out
 
@@ -319,15 +329,6 @@ class VDiffEngine:
     def _check_backward_support(self):
         if self.precise:
             raise NotImplementedError("input gradient runs in the 16-bit modes (bf16 / f16)")
-
-    def _wt(self, key, weight, cin_pad=None):
-        """Packed weights of the input-gradient convolution of `weight` [Cout, Cin, k, k]: [Cin, Cout, k, k] with both taps flipped."""
-        if key not in self.w:
-            w = weight.detach().float().permute(1, 0, 2, 3)
-            if w.shape[-1] == 3:
-                w = w.flip(2, 3)
-            self.w[key] = PackedLinear(w.contiguous(), None, self.dt, self.device, cin_pad=cin_pad)
-        return self.w[key]
 
     def _res_train_cond(self, l: Res, p, x, x1, mod, tape):
         """cc12m_1.py:46-61: conv -> GroupNorm(1, C, affine=False) -> Modulation2d -> ReLU -> conv [-> the same again] + skip, with the
@@ -373,24 +374,12 @@ class VDiffEngine:
     def _attn_train(self, l: Attn, p, x, tape):
         dt, w = self.dt, self.w
         n, hh, ww, c = x.shape
-        d = self.spec.get("head_dim", 64)
-        t, heads = hh * ww, c // d
+        t, heads = hh * ww, c // self.spec.get("head_dim", 64)
         hn = x
         if self.spec.get("attn_norm", True):
             g, b = w[p + ".gn"]
             hn = ops.group_norm(x, g, b, 1, dt)
-        qkv = ops.igemm(hn.view(n * t, c), w[p + ".qkv"])
-        if d == 64:                                  # flash-style forward keeping the log-sum-exp (csrc/attn.hip)
-            tp32 = (t + 31) // 32 * 32
-            aws = torch.empty((6, n * heads, tp32, 64), dtype=x.dtype, device=x.device)
-            lse = torch.empty((n * heads, tp32), dtype=torch.float32, device=x.device)
-            a = torch.empty((n * t, c), dtype=x.dtype, device=x.device)
-            call("pmi_vit_attn_fwd", ptr(qkv), ptr(aws), ptr(lse), ptr(a), n, t, heads, 64.0 ** -0.5, dt)
-            saved = (aws, lse, a)
-        else:                                        # other head dims (wikiart: 128): batched GEMMs, the softmax is kept
-            a, pm = ops.attention_train(qkv.view(n, t, 3 * c), heads, dt)
-            a = a.view(n * t, c)
-            saved = (qkv, pm)
+        a, saved = ops.self_attention_train(ops.igemm(hn.view(n * t, c), w[p + ".qkv"]), n, t, heads, dt)
         y = ops.igemm(a, w[p + ".out"], residual=x.view(n * t, c)).view(n, hh, ww, c)
         tape.append(("attn", l, p, x, saved))
         return y
@@ -422,40 +411,22 @@ class VDiffEngine:
     def forward_train(self, images: torch.Tensor, t: torch.Tensor, clip_embed: Optional[torch.Tensor] = None):
         """As forward(), keeping what backward() needs.  Returns (v NCHW fp32, tape)."""
         self._check_backward_support()
-        if not images.is_cuda:
-            raise RuntimeError("VDiffEngine runs on a HIP device only (no CPU fallback)")
-        dt, dev = self.dt, self.device
-        images = images.float().contiguous()
-        n, _, hh, ww = images.shape
-        t = t.to(device=dev, dtype=torch.float32).contiguous()
-        mod = None
-        if self.cond:
-            if clip_embed is None:
-                raise ValueError("this model is CLIP-conditioned: clip_embed is required")
-            mod = self._mapping(t, clip_embed)                 # no gradient flows to the conditioning: it only scales / shifts
-        planes = torch.empty((n, 16), dtype=torch.float32, device=dev)
-        tf = t
-        if self.spec.get("t_input") == "log_snr":       # wikiart_256.py:288-292
-            tf = torch.log(torch.cos(t * (torch.pi / 2)) ** 2 / torch.sin(t * (torch.pi / 2)) ** 2).contiguous()
-        call("pmi_fourier_features", ptr(tf), ptr(self.tw), ptr(planes), n, 8)
-        x = torch.empty((n, hh, ww, 24), dtype=_hip.TORCH_DTYPE[dt], device=dev)
-        call("pmi_prep_input", ptr(images), ptr(planes), 16, ptr(x), n, hh, ww, 24, dt)
+        mod, x = self._embed_input(images, t, clip_embed)
         tape = []
         y = self._run_train(self.spec["net"], "net", x, tape, mod)
-        out = torch.empty((n, 3, hh, ww), dtype=torch.float32, device=dev)
-        call("pmi_finish_output", ptr(y), y.shape[-1], ptr(out), n, hh, ww, 3)
-        return out, tape
+        return self._output(y), tape
 
     def _mask(self, g, y):
         """g * (y > 0) in place: y is a post-ReLU tensor, its sign is the mask."""
         call("pmi_act_bwd", ptr(g), ptr(y), ptr(g), g.numel(), ACT_RELU, self.dt)
         return g
 
-    def _film_norm_back(self, xpre, d, mod, off):
-        """d (gradient wrt Modulation2d's output, ReLU mask already applied) -> gradient wrt the GroupNorm(1, C) input xpre."""
+    def _film_norm_back(self, xpre, d, mod, off, d_mod):
+        """d (gradient wrt Modulation2d's output, ReLU mask already applied) -> gradient wrt the GroupNorm(1, C) input xpre; adds this
+        layer's d scale | d shift into d_mod unless it is None."""
         n, hh, ww, c = xpre.shape
-        if self._dmod is not None:
-            self._cond_grad_layer(xpre, d, off)
+        if d_mod is not None:
+            self._cond_grad_layer(xpre, d, off, d_mod)
         out = torch.empty_like(xpre)
         scale = mod[:, off:]                                                     # [N, >= C] view: (scale | shift) of this layer
         part = torch.empty((n, _hip.lib().pmi_gn1_bwd_partials(hh * ww, c), 4), dtype=torch.float64, device=xpre.device)
@@ -467,7 +438,7 @@ class VDiffEngine:
     # gradient wrt out, d shift = sum_p d and d scale = sum_p d xhat = r (sum_p d x - mu sum_p d).  The per-channel sums are one streaming pass
     # (pmi_gn_bwd_stats), the per-sample moments come from the forward statistics pass; all layers accumulate into one [N, sum 2C] row that
     # goes back through the mapping network (four tiny fp32 GEMMs on the exact-fp32 MFMA, recomputed forward for the ReLU masks).
-    def _cond_grad_layer(self, xpre, d, off):
+    def _cond_grad_layer(self, xpre, d, off, d_mod):
         n, hh, ww, c = xpre.shape
         hw, dev, dt = hh * ww, xpre.device, self.dt
         nchunk = max(1, min(hw // 8, (1024 + n - 1) // n))
@@ -482,8 +453,8 @@ class VDiffEngine:
         wb = torch.empty((n, nchunk, c, 2), dtype=torch.float32, device=dev)
         call("pmi_gn_bwd_stats", ptr(xpre), None, c, ptr(d), ptr(one), ptr(zero), ACT_NONE, ptr(wb), n, hw, c, nchunk, dt)
         ab = wb.double().sum(dim=1)                                        # [n, c, 2]: sum_p d, sum_p d x
-        self._dmod[:, off:off + c] += (r[:, None] * (ab[..., 1] - mu[:, None] * ab[..., 0])).float()
-        self._dmod[:, off + c:off + 2 * c] += ab[..., 0].float()
+        d_mod[:, off:off + c] += (r[:, None] * (ab[..., 1] - mu[:, None] * ab[..., 0])).float()
+        d_mod[:, off + c:off + 2 * c] += ab[..., 0].float()
 
     def _mapping_back(self, t, clip_embed, d_mod, sd):
         """d loss / d clip_embed from d loss / d (every layer's scale | shift): back through Modulation2d.layer, the two ResLinearBlocks
@@ -521,55 +492,46 @@ class VDiffEngine:
         d_cen = d_xin[:, :dim]
         return (dim ** 0.5 / nrm) * (d_cen - chat * (chat * d_cen).sum(dim=1, keepdim=True))
 
-    def _res_back(self, rec, g, sd, first):
+    def _res_back(self, rec, g, sd, d_mod, first):
         _, l, p, h1, r2, two, hpre, h2pre, mod = rec
         j = 4 if self.cond else 2
+        w, dt, dev = self.w, self.dt, self.device
         w2 = sd[p + f".main.{j}.weight"]
         w1 = sd[p + ".main.0.weight"]
         if l.last:
             d2 = g                                                               # [N,H,W,8]: 3 channels + padding
-            c2t = self._wt(p + ".c2T", w2, cin_pad=8)
+            c2t = ops.packed_dx(w, p + ".c2T", w2, dt, dev, cin_pad=8)
         else:
             d2 = self._mask(g.clone(), r2)
             if self.cond:
-                d2 = self._film_norm_back(h2pre, d2, mod, l.mod2)
-            c2t = self._wt(p + ".c2T", w2)
+                d2 = self._film_norm_back(h2pre, d2, mod, l.mod2, d_mod)
+            c2t = ops.packed_dx(w, p + ".c2T", w2, dt, dev)
         dh1 = self._mask(ops.igemm(d2, c2t), h1)
         if self.cond:
-            dh1 = self._film_norm_back(hpre, dh1, mod, l.mod1)
+            dh1 = self._film_norm_back(hpre, dh1, mod, l.mod1, d_mod)
         has_skip = l.cin != l.cout
         skw = sd[p + ".skip.weight"] if has_skip else None
         spad = 8 if l.last else None
         if not two:
-            gs = ops.igemm(g, self._wt(p + ".skipT", skw, cin_pad=spad)) if has_skip else g
-            return ops.igemm(dh1, self._wt(p + ".c1T", w1), residual=gs, out_f32=first), None
+            gs = ops.igemm(g, ops.packed_dx(w, p + ".skipT", skw, dt, dev, cin_pad=spad)) if has_skip else g
+            return ops.igemm(dh1, ops.packed_dx(w, p + ".c1T", w1, dt, dev), residual=gs, out_f32=first), None
         half = l.cin // 2                                                        # conv1 / skip read cat([main(x), x]): one dX per source
         outs = []
         for k in range(2):
             sl = slice(k * half, (k + 1) * half)
-            gs = ops.igemm(g, self._wt(p + f".skipT{k}", skw[:, sl], cin_pad=spad))
-            outs.append(ops.igemm(dh1, self._wt(p + f".c1T{k}", w1[:, sl]), residual=gs))
+            gs = ops.igemm(g, ops.packed_dx(w, p + f".skipT{k}", skw[:, sl], dt, dev, cin_pad=spad))
+            outs.append(ops.igemm(dh1, ops.packed_dx(w, p + f".c1T{k}", w1[:, sl], dt, dev), residual=gs))
         return outs[0], outs[1]
 
     def _attn_back(self, rec, g, sd):
         _, l, p, x, saved = rec
         dt = self.dt
         n, hh, ww, c = x.shape
-        d = self.spec.get("head_dim", 64)
-        t, heads = hh * ww, c // d
+        t, heads = hh * ww, c // self.spec.get("head_dim", 64)
         g2 = g.reshape(n * t, c)
-        da = ops.igemm(g2, self._wt(p + ".outT", sd[p + ".out_proj.weight"]))
-        if d == 64:
-            aws, lse, a = saved
-            tp32 = (t + 31) // 32 * 32
-            bws = torch.empty((2, n * heads, tp32, 64), dtype=x.dtype, device=x.device)
-            delta = torch.empty((n * heads, tp32), dtype=torch.float32, device=x.device)
-            dqkv = torch.empty((n * t, 3 * c), dtype=x.dtype, device=x.device)
-            call("pmi_vit_attn_bwd", ptr(aws), ptr(lse), ptr(a), ptr(da), ptr(bws), ptr(delta), ptr(dqkv), n, t, heads, 64.0 ** -0.5, dt)
-        else:
-            qkv, pm = saved
-            dqkv = ops.attention_backward(qkv.view(n, t, 3 * c), pm, da.view(n, t, c), heads, dt).view(n * t, 3 * c)
-        dhn = ops.igemm(dqkv, self._wt(p + ".qkvT", sd[p + ".qkv_proj.weight"]))
+        da = ops.igemm(g2, ops.packed_dx(self.w, p + ".outT", sd[p + ".out_proj.weight"], dt, self.device))
+        dqkv = ops.self_attention_backward(saved, da, n, t, heads, dt)
+        dhn = ops.igemm(dqkv, ops.packed_dx(self.w, p + ".qkvT", sd[p + ".qkv_proj.weight"], dt, self.device))
         gx = torch.empty_like(x)
         if self.spec.get("attn_norm", True):
             part = torch.empty((n, _hip.lib().pmi_gn1_bwd_partials(t, c), 4), dtype=torch.float64, device=x.device)
@@ -578,19 +540,20 @@ class VDiffEngine:
             call("pmi_add16", ptr(dhn), ptr(g2), ptr(gx), gx.numel(), dt)
         return gx
 
-    def _back(self, tape, g, sd, outermost=False):
-        """Gradient wrt the input of the block sequence recorded in `tape`, given g = gradient wrt its output."""
+    def _back(self, tape, g, sd, d_mod, outermost=False):
+        """Gradient wrt the input of the block sequence recorded in `tape`, given g = gradient wrt its output; d_mod (or None) accumulates
+        the gradient wrt every Modulation2d's scale | shift."""
         g1 = None
         for idx in range(len(tape) - 1, -1, -1):
             rec = tape[idx]
             kind = rec[0]
             if kind == "res":
                 assert g1 is None
-                g, g1 = self._res_back(rec, g, sd, first=outermost and idx == 0)
+                g, g1 = self._res_back(rec, g, sd, d_mod, first=outermost and idx == 0)
             elif kind == "skip":
                 assert g1 is not None, "a SkipBlock is always followed by the block that reads its concat"
                 g_inner, g_x = (g1, g) if self.spec.get("skip_first") else (g, g1)
-                gm = self._back(rec[1], g_inner, sd)                             # through main(x)
+                gm = self._back(rec[1], g_inner, sd, d_mod)                      # through main(x)
                 out = torch.empty_like(gm)
                 call("pmi_add16", ptr(gm), ptr(g_x), ptr(out), gm.numel(), self.dt)
                 g, g1 = out, None
@@ -599,16 +562,10 @@ class VDiffEngine:
                 if kind == "attn":
                     g = self._attn_back(rec, g, sd)
                 elif kind == "down":
-                    n, h, w_, c = g.shape
-                    out = torch.empty((n, 2 * h, 2 * w_, c), dtype=g.dtype, device=g.device)
-                    call("pmi_avgpool2_bwd", ptr(g), ptr(out), n, 2 * h, 2 * w_, c, self.dt)
-                    g = out
+                    g = ops.avgpool2_bwd(g, self.dt)
                 elif kind == "up":
-                    n, h, w_, c = g.shape
-                    out = torch.empty((n, h // 2, w_ // 2, c), dtype=g.dtype, device=g.device)
-                    call("pmi_upsample_nearest2_bwd" if self.spec.get("up_mode") == "nearest" else "pmi_upsample_bilinear2_bwd",
-                         ptr(g), ptr(out), n, h // 2, w_ // 2, c, self.dt)
-                    g = out
+                    up_bwd = ops.upsample_nearest2_bwd if self.spec.get("up_mode") == "nearest" else ops.upsample_bilinear2_bwd
+                    g = up_bwd(g, self.dt)
         assert g1 is None
         return g
 
@@ -616,31 +573,21 @@ class VDiffEngine:
     def backward(self, tape, d_v: torch.Tensor, state_dict, cond_grad=None):
         """d loss / d images (NCHW fp32, images in [0, 1]) from d loss / d v (NCHW fp32 [N, 3, H, W]) and the tape of forward_train().
         `state_dict`: the model's parameters (reference key names) -- the transposed weight packings are built from it on first use.
-        f16 engines scale the gradient by a power of two (largest incoming value -> 1) on the way in and back on the way out: image
-        gradients of a CLIP loss are ~1e-6 and would flush to zero in f16; bf16 needs no scaling.
+        f16 engines scale the gradient by a power of two on the way in and back on the way out (ops.grad_to_nhwc); bf16 needs no scaling.
         cond_grad = (t [N], clip_embed [N, D]) of a conditioned net: also returns d loss / d clip_embed -> (d_images, d_clip_embed)."""
         self._check_backward_support()
-        dev, dt = self.device, self.dt
-        n, _, hh, ww = d_v.shape
+        dev, n = self.device, d_v.shape[0]
+        d_mod = None
         if cond_grad is not None:
             if not self.cond:
                 raise ValueError("cond_grad: this net takes no conditioning")
-            self._dmod = torch.zeros((n, sum(state_dict[k].shape[0] for k in self._mod_keys)), dtype=torch.float32, device=dev)
-        scale = 1.0
-        if dt == _hip.DT_F16:                         # keep the f16 gradient tensors in range: largest incoming value -> 1 (power of two: exact)
-            amax = float(d_v.abs().max())
-            if amax > 0.0 and amax == amax:
-                scale = 2.0 ** max(-24, min(24, -int(torch.tensor(amax).log2().ceil())))
-        g = torch.zeros((n, hh, ww, 8), dtype=_hip.TORCH_DTYPE[dt], device=dev)                # 3 channels + padding (layout only)
-        g[..., :3] = (d_v.to(dev).float() * scale).permute(0, 2, 3, 1)
+            d_mod = torch.zeros((n, sum(state_dict[k].shape[0] for k in self._mod_keys)), dtype=torch.float32, device=dev)
+        g, scale = ops.grad_to_nhwc(d_v, self.dt, dev)                                          # 3 channels + padding
         sd = {k: v.detach() for k, v in state_dict.items()}
-        gx = self._back(tape, g, sd, outermost=True)                                            # fp32 [N,H,W,20]: d / d (x, Fourier planes)
-        out = torch.empty((n, 3, hh, ww), dtype=torch.float32, device=dev)
-        call("pmi_finish_output", ptr(gx), gx.shape[-1], ptr(out), n, hh, ww, 3)
-        if cond_grad is not None:
-            d_mod, self._dmod = self._dmod / scale, None
-            t_, ce_ = cond_grad
-            d_ce = self._mapping_back(t_.to(device=dev, dtype=torch.float32).contiguous(), ce_, d_mod.contiguous(), sd)
-            return out * (2.0 / scale), d_ce
-        return out * (2.0 / scale)                                                              # x = 2 * images - 1
+        gx = self._back(tape, g, sd, d_mod, outermost=True)                                     # fp32 [N,H,W,20]: d / d (x, Fourier planes)
+        out = ops.grad_to_nchw(gx, 3, 2.0 / scale)                                              # x = 2 * images - 1
+        if cond_grad is None:
+            return out
+        t_, ce_ = cond_grad
+        return out, self._mapping_back(t_.to(device=dev, dtype=torch.float32).contiguous(), ce_, (d_mod / scale).contiguous(), sd)
 

@@ -238,3 +238,41 @@ def test_sd_schedule_indices_match_reference_method_on_sd_tables():
     assert torch.equal(m.schedule_indices(n_steps=50).cpu(), g["idx_50"])
     assert torch.equal(m.schedule_indices().cpu(), g["idx_500"])
     assert torch.equal(m.schedule_indices(n_steps=20, from_index=500, to_index=20).cpu(), g["idx_20_500_20"])
+
+
+@pytest.mark.parametrize("kind", ["linear", "conv1d_k1", "conv1x1", "conv3x3", "conv3x3_rows"])
+def test_packed_dx_weights_give_autograd_input_gradient(kind):
+    """ops.packed_dx: conv2d of a gradient with the packed [Cin, Cout, k, k] weights (padding k // 2) is float64 autograd's dX."""
+    import torch.nn.functional as F
+    from perceptor_amd import _hip
+    from perceptor_amd.engine import ops
+    g = torch.Generator().manual_seed(5)
+    cout, cin = 12, 5
+    shape = {"linear": (cout, cin), "conv1d_k1": (cout, cin, 1), "conv1x1": (cout, cin, 1, 1)}.get(kind, (cout, cin, 3, 3))
+    w = torch.randint(-4, 5, shape, generator=g).double()             # small integers: exact in f16 and in every float64 sum
+    rows = 8 if kind == "conv3x3_rows" else None
+    lin = ops.packed_dx({}, "k", w, _hip.DT_F16, "cpu", rows=rows)
+    k = 3 if w.ndim == 4 and w.shape[-1] == 3 else 1
+    wt = lin.w.double().view(lin.n_p, k * k, lin.cin_p)[:lin.cout, :, :lin.cin].reshape(lin.cout, k, k, lin.cin).permute(0, 3, 1, 2)
+    assert wt.shape == ((rows or cin), cout, k, k)
+    w4 = w.reshape(cout, cin, k, k)
+    x = torch.randint(-3, 4, (2, cin, 6, 7), generator=g).double().requires_grad_()
+    dy = torch.randint(-3, 4, (2, cout, 6, 7), generator=g).double()
+    F.conv2d(x, w4, padding=k // 2).backward(dy)
+    dx = F.conv2d(dy, wt, padding=k // 2)
+    assert torch.equal(dx[:, :cin], x.grad)
+    assert not dx[:, cin:].any()                                      # the padded rows
+    assert ops.packed_dx({"k": lin}, "k", w * 2, _hip.DT_F16, "cpu") is lin   # cached under its key
+
+
+def test_f16_grad_scale_rule():
+    from perceptor_amd.engine.ops import f16_grad_scale
+    nan, inf = float("nan"), float("inf")
+    assert f16_grad_scale([1.0]) == 1.0 and f16_grad_scale([0.25, 0.0]) == 4.0          # exactly a power of two -> max lands on 1
+    above = float(torch.tensor(0.25, dtype=torch.float32).nextafter(torch.tensor(1.0)))  # one float32 ulp above a power of two
+    assert f16_grad_scale([above]) == 2.0
+    assert f16_grad_scale([3e-6, 1e-6]) == 2.0 ** 18
+    assert f16_grad_scale([0.0, 0.0]) == 1.0
+    assert f16_grad_scale([1e-3, nan]) == 1.0 and f16_grad_scale([nan, 1e-3]) == 1.0   # a NaN in any sample
+    assert f16_grad_scale([1e-3, inf]) == 1.0
+    assert f16_grad_scale([1e-30]) == 2.0 ** 24 and f16_grad_scale([1e30]) == 2.0 ** -24

@@ -56,7 +56,7 @@ def main():
     p.add_argument("--no-step", action="store_true")
     p.add_argument("--aten", action="store_true")
     a = p.parse_args()
-    from perceptor_amd.engine import sd
+    from perceptor_amd.engine import ops, sd
     from perceptor_amd.utils.synth import seeded_noise, synth_state_dict
     dev = torch.device("cuda:0")
     res = {}
@@ -75,8 +75,8 @@ def main():
         k = f"decoder.up_blocks.{i}.upsamplers.0.conv"
         c = chans[i]
         g = torch.randn((n, 2 * h, 2 * h, c), generator=torch.Generator(dev).manual_seed(100 + i), device=dev).to(torch.bfloat16)
-        f1 = lambda: eng._up_back(k, g, w, fused=True)
-        f0 = lambda: eng._up_back(k, g, w, fused=False)
+        f1 = lambda: eng._up_back(k, g, w)
+        f0 = lambda: ops.upsample_nearest2_bwd(ops.igemm(g, ops.packed_dx(eng.w, k + "T", w[k + ".weight"], eng.dt, dev)), eng.dt)
         r1, r0 = f1(), f0()                                        # (packs both weight sets)
         diff = float((r1.float() - r0.float()).norm() / r0.float().norm())
         t1, t0 = [], []
