@@ -69,9 +69,11 @@ typedef struct {
   int32_t stats_p;     /* partial rows per image = pmi_igemm_stats_rows(); 0 = no statistics */
   int32_t splitk;      /* <= 1: none; else K is split over grid.z and reduced by a second kernel (see pmi_igemm_splitk) */
   int32_t reserved;
-  const void* Bf;      /* optional: the same weights in MFMA fragment order for the weights-direct conv3x3 kernel (csrc/conv_wd.hip),
-                        * [N/32][Cin/ck][3 dx][ck/16][3 dy][64 lanes][8] 16-bit with ck = 64 (tile config 4) or 32 (config 5); NULL = not packed */
-  int32_t split_out;   /* "precise" mode (dtype 2): D (and a 16-bit R) hold hi + lo f16 pairs in groups of split_out (8 or 32) logical channels,
+  const void* Bf;      /* optional: the same weights in MFMA fragment order for the weights-direct kernels; NULL = not packed.  conv3x3
+                        * (csrc/conv_wd.hip): config 4 [N/32][Cin/64][3 dx][4][3 dy][64 lanes][8], configs 6 / 7 (16x16x32 MFMA, ck = 64 / 32)
+                        * [N/32][Cin/ck][3 dx][ck/32][3 dy][2][64 lanes][8], config 8 [N/32][ceil(9 Cin / 32)][2][64 lanes][8]; the GEMM
+                        * (csrc/gemm_wd.hip): see pmi_gemm_wd_eligible */
+  int32_t split_out;   /* "precise" mode (dtype 2): D (and a 16-bit R) hold hi + lo f16 pairs in groups of split_out (32, or 8 / 16 / 24 = N) logical channels,
                         * ldd / ldr count 16-bit elements of the 2N-wide rows; 0 = plain.  A split INPUT needs no flag: it is a tensor with 2 Cin
                         * channels whose weights are duplicated along K by the caller.  Generic kernel only (no LDS-halo config). */
   int32_t split_in;    /* 1: the inputs are precise (hi + lo) tensors whose 2 Cin physical channels are the K dimension (C0 / C1 / K count them; weights
@@ -88,8 +90,11 @@ typedef struct {
 } pmi_igemm_args;
 int pmi_igemm(const pmi_igemm_args* a, pmi_stream_t stream);
 /* >= 0 when an LDS-halo conv3x3 kernel takes this shape.  csrc/conv3x3.hip: tile config 0: 8x32 px x 256 ch, 1: 16x32 x 128, 2: 8x32 x 128 with two
- * workgroups per CU, 3: 8x32 px x <= 32 output channels; csrc/conv_wd.hip (weights-direct, needs Bf != NULL): 4: 8x32 px x 256 ch, 5: 8x32 px x 128 ch;
- * -1 when pmi_igemm uses the generic implicit-GEMM kernel (which has no fused prologue). */
+ * workgroups per CU, 3: 8x32 px x <= 32 output channels (also a split input with fp32 output, N <= 32: a plain K over the 2 Cin physical
+ * channels); csrc/conv_wd.hip (weights-direct, needs Bf != NULL): 4: 8x32 px x 256 ch (32x32x16 MFMA), 6: 8x32 px x 256 ch (16x16x32 MFMA,
+ * 64-channel chunks), 7: 8x32 px x 128 ch (16x16x32, 32-channel chunks, also a masked Cout tail), 8: at most 32 input channels, one source,
+ * the whole K in registers.  Split (precise / mixed) outputs take configs 6 / 7 / 8 only.  -1 when pmi_igemm uses the generic implicit-GEMM
+ * kernel (which has no fused prologue). */
 int pmi_conv3x3_halo_config(const pmi_igemm_args* a);
 /* 1 when the weights-direct GEMM (csrc/gemm_wd.hip) takes this call: plain GEMM (taps 1, one source, no per-sample bias / statistics / prologue),
  * K % 128 == 0, N % 256 == 0 and Bf = the weights in its fragment order [N/32][K/128][4][2][64 lanes][8] */

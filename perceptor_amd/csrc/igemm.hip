@@ -634,7 +634,9 @@ extern "C" int pmi_igemm(const pmi_igemm_args* a, pmi_stream_t stream) {
   if (a->stride != 1 && a->stride != 2) return bad_arg(__LINE__);
   if (a->K != a->taps * (a->C0 + a->C1)) return bad_arg(__LINE__);
   if (a->R && (a->ldr & 3)) return bad_arg(__LINE__);
-  if (a->split_out && ((a->split_out != 8 && a->split_out != 32) || a->out_f32 || (a->N % a->split_out) || a->batch > 1)) return bad_arg(__LINE__);
+  // (split_out: the group width ops.split_group gives a tensor of N channels -- 32, or N itself for 8 / 16 / 24; the epilogues write 4-channel
+  // runs at split_off(n, G), which never straddle a group for G % 4 == 0)
+  if (a->split_out && ((a->split_out & 7) || a->split_out > 32 || a->out_f32 || (a->N % a->split_out) || a->batch > 1)) return bad_arg(__LINE__);
   if ((unsigned)a->split_in > 2u) return bad_arg(__LINE__);
   // (a fused prologue over split tensors and the single-operand form split_in = 2 exist in the weights-direct conv3x3 configs only: the
   // check behind the config query below rejects every other route)

@@ -60,9 +60,12 @@ class PackedLinear:
 
     dt = precise (DT_F16X2): the inputs are hi + lo tensors with 2*Cin channels per pixel ([hi G | lo G] per group of G channels), so
     the f16 weights are duplicated along K in the same pattern: W*hi + W*lo accumulates in fp32 on the MFMA.  `sources` gives the
-    logical channel counts of a two-pointer concat input (each source is its own precise tensor with its own grouping)."""
+    logical channel counts of a two-pointer concat input (each source is its own precise tensor with its own grouping).
+    concat_sources = False keeps two-source fp32 weights a two-pointer layer (their low part rounded away, with a warning): the mixed
+    mode's fused-prologue configs read the two sources through their own pointers."""
 
-    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor], dt: int, device, cin_pad: Optional[int] = None, sources=None):
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor], dt: int, device, cin_pad: Optional[int] = None, sources=None,
+                 concat_sources: bool = True):
         w = weight.detach().float()
         if w.ndim == 3:   # Conv1d k=1
             w = w[..., 0]
@@ -77,6 +80,7 @@ class PackedLinear:
         self.split = dt == DT_F16X2
         self.cin_l = self.cin_p                      # logical input channels
         self.self_concat = False
+        self.concat_inputs = False                   # self_concat over two sources: igemm() joins a0 | a1 into one split tensor
         if self.split:
             def dup(wt, lo_zero=False):              # [N, taps, C] -> [N, taps, 2C] in the [hi G | lo G] pattern of the input
                 parts, o = [], 0
@@ -99,13 +103,17 @@ class PackedLinear:
             # fp16-checkpoint weights of a long-K layer have a few values under the f16 subnormal grid (< 2^-14: they lose < 3e-8 absolute,
             # ~4e-8 of the norm) -- the max-element test of round 2 doubled K for every such layer (4x the MFMA work, for nothing).
             if float(w_lo.norm()) > 2.0 ** -22 * float(w_hi.norm()):
-                if sources is not None:
+                # two sources whose groupings are all 32 wide: their split tensors concatenate into one split tensor with the same
+                # [hi 32 | lo 32] grouping, so the layer is the single-source one below and igemm() concatenates a0 | a1 before the call
+                concat_ok = sources is None or (concat_sources and all(cs % 32 == 0 for cs in sources))
+                if not concat_ok:
                     import warnings
                     warnings.warn("precise mode: fp32 weights of a two-source (concat) convolution are rounded to f16")
                 else:
                     # second K block over the SAME input tensor (passed again as the second source): W_lo * x_hi
                     packed = torch.cat([packed, dup(w_lo, lo_zero=True)], dim=2)
                     self.self_concat = True
+                    self.concat_inputs = sources is not None
                     self.cin_p = 2 * self.cin_p
         self.w = packed.reshape(self.n_p, -1).to(device=device, dtype=_hip.TORCH_DTYPE[dt]).contiguous()
         self.b = None
@@ -199,7 +207,7 @@ class MixedLinear:
     def dbl(self) -> PackedLinear:
         if self._dbl is None:
             w, b, dev, src, cp = self._args
-            self._dbl = PackedLinear(w, b, DT_F16X2, dev, cin_pad=cp, sources=src)
+            self._dbl = PackedLinear(w, b, DT_F16X2, dev, cin_pad=cp, sources=src, concat_sources=False)
         return self._dbl
 
 
@@ -347,6 +355,9 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
     act_grad_of / act_grad: the output is multiplied by act'(act_grad_of) -- both only where fused_mlp_epilogues(lin) is True."""
     dt = lin.dt
     conv = a0.ndim == 4
+    if lin.concat_inputs and a1 is not None and prologue is None:
+        # (a prologue materialises one applied tensor from both sources below: no copy needed there)
+        a0, a1 = torch.cat([a0, a1], dim=-1), None
     c0 = a0.shape[-1]
     c1 = a1.shape[-1] if a1 is not None else 0
     assert (c0 + c1) * (2 if lin.self_concat else 1) == lin.cin_p, (c0, c1, lin.cin_p)
@@ -410,6 +421,10 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
         if HALO_ENABLED and not lin.split and _hip.lib().pmi_conv3x3_halo_config(C.byref(a)) >= 0:
             a.pro_a, a.pro_b, a.pro_act = ptr(ca), ptr(cb), pact
         else:   # not eligible: materialise act(x*a+b) with the streaming kernel, then convolve
+            if lin.split and a1 is not None and (c0 // 2) % 32 + (c1 // 2) % 32:
+                # the applied tensor is ONE precise tensor grouped by split_group(C0 + C1); weights duplicated per source match it only
+                # when both sources are grouped by 32 as well
+                raise ValueError(f"precise two-source prologue: sources of {c0 // 2} + {c1 // 2} channels are not both multiples of 32")
             n_, h_, w_, _ = a0.shape
             y = _empty((n_, h_, w_, c0 + c1), a0.dtype, a0.device)
             lc0, lc = (c0 // 2, (c0 + c1) // 2) if lin.split else (c0, c0 + c1)       # logical channel counts
@@ -463,7 +478,8 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
         kind = "conv" if conv and (lin.taps == 9 or up or stride == 2) else "gemm"
         desc = f"{kind} M={m} N={lin.n_p} K={lin.K} taps={lin.taps}{' up' if up else ''}{' s2' if stride == 2 else ''} splitk={a.splitk}" \
                f" halo={_hip.lib().pmi_conv3x3_halo_config(C.byref(a)) if HALO_ENABLED else -1} wd={int(bool(a.Bf) and bool(_hip.lib().pmi_gemm_wd_eligible(C.byref(a))))}" \
-               f"{' res' if residual is not None else ''}{' f32out' if a.out_f32 else ''}{' nbias' if nbias is not None else ''}{' stats' if a.stats else ''}"
+               f"{' res' if residual is not None else ''}{' f32out' if a.out_f32 else ''}{' nbias' if nbias is not None else ''}{' stats' if a.stats else ''}" \
+               f"{' split_in' if a.split_in else ''}{' split_out' if a.split_out else ''}{' self_concat' if lin.self_concat else ''}"
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         call("pmi_igemm", C.byref(a))
