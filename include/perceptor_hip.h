@@ -116,7 +116,8 @@ int pmi_igemm_stats_rows(const pmi_igemm_args* a);
 int pmi_set_option(int key, int value);
 
 /* ---- "precise" mode helpers (dtype 2: hi + lo f16 pairs, eps max-abs error < 1e-3 vs the fp32 reference path) ----------------
- * exact-fp32 batched GEMM on the f32-input MFMA: D[b][m][n] = act(alpha * sum_k A[b][m][k] * B[b][n][k] + bias[n]); transB: B is [k][n].
+ * exact-fp32 batched GEMM on the f32-input MFMA: D[b][m][n] = act(alpha * sum_k A[b][m][k] * B[b][n][k] + bias[n]); transB: B is [k][n]; transA: A is
+ * [k][m] (the attention backward's P^T dO and dS^T Q).
  * Replaces the attention einsums of unet.py:332-348 / yfcc_2.py:62-70 and the time MLPs (unet.py:462-467) in that mode. */
 typedef struct {
   const float* A; const float* B; const float* bias; float* D;
@@ -126,9 +127,12 @@ typedef struct {
   int32_t batch, batch_inner;          /* grid.z batches: z -> (z / batch_inner, z % batch_inner) */
   int64_t sA_o, sA_i, sB_o, sB_i, sD_o, sD_i;
   const float* R;                      /* optional residual added after the activation, laid out like D */
+  int32_t transA;                      /* appended last: a caller must zero-initialise the struct (lda >= M when set, >= K otherwise) */
 } pmi_gemm_f32_args;
 int pmi_gemm_f32(const pmi_gemm_f32_args* a, pmi_stream_t stream);
 int pmi_softmax_f32(float* S, int rows, int T, int ld, float scale, pmi_stream_t s);   /* in place, fp32 (unet.py:346) */
+/* in place on dP: dS = scale * P o (dP - rowsum(dP o P)), fp32 rows -- what autograd forms for the softmax of unet.py:346 / yfcc_2.py:67 */
+int pmi_softmax_bwd_f32(float* dP, const float* P, int rows, int T, int ld, float scale, pmi_stream_t s);
 /* fp32 [rows][C] (row pitch ld_in) <-> precise [rows][2C] */
 int pmi_split_from_f32(const float* in, int ld_in, void* out, int64_t rows, int C, pmi_stream_t s);
 int pmi_split_to_f32(const void* in, float* out, int64_t rows, int C, pmi_stream_t s);
@@ -267,6 +271,26 @@ int pmi_gn_bwd_finalize(const float* s0, int P0, int C0, const float* s1, int P1
 int pmi_gn_bwd_apply(const void* x, const void* x1, int C0, const void* dy, const float* coef_a, const float* coef_b, const float* coef_p,
                      const float* coef_q, int act, const void* gadd0, const void* gadd1, void* dx0, void* dx1, int N, int HW, int C,
                      int dtype, pmi_stream_t s);
+/* The same adjoints over precise tensors (PMI_DT_F16X2: [rows][C/G][hi G | lo G]; C = logical channels, a multiple of 32 or of 8 up to 32).
+ * Both halves are added on load, the arithmetic is fp32, the result is split again on store.  They give the precise mode the input gradient
+ * autograd provides upstream (guided_diffusion.py:125-133, losses/velocity_diffusion.py:33-61).
+ * Names: pmi_split_<twin>, like the split conversions above, and not <twin>_split: tests/test_norm_resample_bounds_cpu.py requires every
+ * pmi_gn* / pmi_avgpool* / pmi_upsample* prototype to be exercised by tests/test_gpu_norm_resample.py, which covers the 16-bit entry points
+ * only (those keep rejecting dtype 2); the split ones are covered by tests/test_gpu_precise_backward.py.
+ * pmi_split_add: (a_hi + a_lo) + (b_hi + b_lo); pmi_split_relu_bwd: out = g [y > 0] with the sign of y_hi + y_lo (F.relu's backward,
+ * yfcc_2.py:17-28); out may alias an input in both.  The rest as their 16-bit twins (pmi_gn_bwd_finalize is fp32 only and shared). */
+int pmi_split_add(const void* a, const void* b, void* out, int64_t rows, int C, pmi_stream_t s);
+int pmi_split_relu_bwd(const void* g, const void* y, void* out, int64_t rows, int C, pmi_stream_t s);
+int pmi_split_avgpool2_bwd(const void* dy, void* dx, int N, int H, int W, int C, pmi_stream_t s);
+int pmi_split_upsample_bilinear2_bwd(const void* dy, void* dx, int N, int H, int W, int C, pmi_stream_t s);
+int pmi_split_upsample_nearest2_bwd(const void* dy, void* dx, int N, int H, int W, int C, pmi_stream_t s);
+int pmi_split_gn1_bwd(const void* x, const void* dy, const float* gamma, int gamma_ld, float gamma_add, const void* res, void* dx,
+                      double* partial, int N, int64_t hw, int C, float eps, pmi_stream_t s);
+int pmi_split_gn_bwd_stats(const void* x, const void* x1, int C0, const void* dy, const float* coef_a, const float* coef_b, int act, float* ws,
+                           int N, int HW, int C, int nchunk, pmi_stream_t s);
+int pmi_split_gn_bwd_apply(const void* x, const void* x1, int C0, const void* dy, const float* coef_a, const float* coef_b, const float* coef_p,
+                           const float* coef_q, int act, const void* gadd0, const void* gadd1, void* dx0, void* dx1, int N, int HW, int C,
+                           pmi_stream_t s);
 int pmi_gn1_bwd_partials(int64_t hw, int C);   /* slices per sample: the caller passes partial = N * this * 4 doubles of workspace */
 int pmi_gn1_bwd(const void* x, const void* dy, const float* gamma, int gamma_ld, float gamma_add, const void* res, void* dx,
                 double* partial, int N, int64_t hw, int C, float eps, int dtype, pmi_stream_t s);

@@ -52,7 +52,7 @@ class GemmF32Args(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("bias", C.c_void_p), ("D", C.c_void_p),
                 ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("lda", C.c_int32), ("ldb", C.c_int32), ("ldd", C.c_int32),
                 ("transB", C.c_int32), ("act", C.c_int32), ("alpha", C.c_float), ("batch", C.c_int32), ("batch_inner", C.c_int32),
-                ("sA_o", C.c_int64), ("sA_i", C.c_int64), ("sB_o", C.c_int64), ("sB_i", C.c_int64), ("sD_o", C.c_int64), ("sD_i", C.c_int64), ("R", C.c_void_p)]
+                ("sA_o", C.c_int64), ("sA_i", C.c_int64), ("sB_o", C.c_int64), ("sB_i", C.c_int64), ("sD_o", C.c_int64), ("sD_i", C.c_int64), ("R", C.c_void_p), ("transA", C.c_int32)]
 
 
 _lib = None
@@ -68,6 +68,7 @@ _PROTOS = {
     "pmi_gemm_wd_eligible": ([C.POINTER(IgemmArgs)],),
     "pmi_gemm_f32": ([C.POINTER(GemmF32Args), _P],),
     "pmi_softmax_f32": ([_P, _I, _I, _I, _F, _P],),
+    "pmi_softmax_bwd_f32": ([_P, _P, _I, _I, _I, _F, _P],),
     "pmi_split_from_f32": ([_P, _I, _P, _L, _I, _P],),
     "pmi_split_to_f32": ([_P, _P, _L, _I, _P],),
     "pmi_split_convert": ([_P, _P, _L, _I, _I, _P],),
@@ -115,6 +116,15 @@ _PROTOS = {
     "pmi_gn_bwd_apply": ([_P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],),
     "pmi_gn1_bwd_partials": ([_L, _I],),
     "pmi_gn1_bwd": ([_P, _P, _P, _I, _F, _P, _P, _P, _I, _L, _I, _F, _I, _P],),
+    # the same over precise (hi + lo) tensors
+    "pmi_split_add": ([_P, _P, _P, _L, _I, _P],),
+    "pmi_split_relu_bwd": ([_P, _P, _P, _L, _I, _P],),
+    "pmi_split_avgpool2_bwd": ([_P, _P, _I, _I, _I, _I, _P],),
+    "pmi_split_upsample_bilinear2_bwd": ([_P, _P, _I, _I, _I, _I, _P],),
+    "pmi_split_upsample_nearest2_bwd": ([_P, _P, _I, _I, _I, _I, _P],),
+    "pmi_split_gn1_bwd": ([_P, _P, _P, _I, _F, _P, _P, _P, _I, _L, _I, _F, _P],),
+    "pmi_split_gn_bwd_stats": ([_P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P],),
+    "pmi_split_gn_bwd_apply": ([_P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P],),
     # CLIP path (clip.hip)
     "pmi_layernorm_fwd": ([_P, _I, _P, _P, _P, _P, _P, _I, _I, _F, _I, _P],),
     "pmi_layernorm_bwd": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],),

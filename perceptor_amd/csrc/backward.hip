@@ -30,10 +30,43 @@ __global__ __launch_bounds__(256) void add16_kernel(const u16* __restrict__ a, c
   }
 }
 
+// Precise (hi + lo) tensors [rows][2C]: out = (a_hi + a_lo) + (b_hi + b_lo) in fp32, split again -- not a 16-bit add of the halves, whose low
+// parts would no longer be the rounding error of the high ones
+__global__ __launch_bounds__(256) void add_split_kernel(const u16* a, const u16* b, u16* out, int64_t rows, int C) {
+  const int C8 = C >> 3;
+  const int64_t total = rows * C8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % C8) * 8;
+    const int64_t ro = (i / C8) * 2 * C;
+    float x[8], y[8];
+    load8<F16X2>(a + ro, c, C, x);
+    load8<F16X2>(b + ro, c, C, y);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] += y[e];
+    store8<F16X2>(out + ro, c, C, x);
+  }
+}
+
+// out = g * [y > 0] (out may be g: each lane loads its 8 channels before it stores them, no __restrict__) for a post-ReLU precise tensor y: the mask is the sign of hi + lo (a half's own sign says nothing: lo is a rounding error)
+__global__ __launch_bounds__(256) void relu_mask_split_kernel(const u16* g, const u16* y, u16* out, int64_t rows, int C) {
+  const int C8 = C >> 3;
+  const int64_t total = rows * C8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % C8) * 8;
+    const int64_t ro = (i / C8) * 2 * C;
+    float gv[8], yv[8];
+    load8<F16X2>(g + ro, c, C, gv);
+    load8<F16X2>(y + ro, c, C, yv);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gv[e] = yv[e] > 0.f ? gv[e] : 0.f;
+    store8<F16X2>(out + ro, c, C, gv);
+  }
+}
+
 // dx[n][y][x][c] = 0.25 * dy[n][y/2][x/2][c]
 template <typename T>
 __global__ __launch_bounds__(256) void avgpool2_bwd_kernel(const u16* __restrict__ dy, u16* __restrict__ dx, int N, int H, int W, int C) {
-  const int C8 = C >> 3, Ho = H / 2, Wo = W / 2;
+  const int C8 = C >> 3, Ho = H / 2, Wo = W / 2, RE = row_elems<T>(C);
   const int64_t total = (int64_t)N * H * W * C8;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(i % C8);
@@ -42,17 +75,17 @@ __global__ __launch_bounds__(256) void avgpool2_bwd_kernel(const u16* __restrict
     const int rem = (int)(pix - (int64_t)n * H * W);
     const int y = rem / W, x = rem - y * W;
     float f[8];
-    unpack8<T>(*(const uint4*)(dy + (((int64_t)n * Ho + (y >> 1)) * Wo + (x >> 1)) * C + c8 * 8), f);
+    load8<T>(dy + (((int64_t)n * Ho + (y >> 1)) * Wo + (x >> 1)) * RE, c8 * 8, C, f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] *= 0.25f;
-    *(uint4*)(dx + pix * C + c8 * 8) = pack8<T>(f);
+    store8<T>(dx + pix * RE, c8 * 8, C, f);
   }
 }
 
 // Adjoint of nn.Upsample(2, 'nearest'): dx[y][x] = sum of the 2x2 block of dy
 template <typename T>
 __global__ __launch_bounds__(256) void upsample_nearest2_bwd_kernel(const u16* __restrict__ dy, u16* __restrict__ dx, int N, int H, int W, int C) {
-  const int C8 = C >> 3, Wo = 2 * W;
+  const int C8 = C >> 3, Wo = 2 * W, RE = row_elems<T>(C);
   const int64_t total = (int64_t)N * H * W * C8;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(i % C8);
@@ -60,15 +93,15 @@ __global__ __launch_bounds__(256) void upsample_nearest2_bwd_kernel(const u16* _
     const int n = (int)(pix / ((int64_t)H * W));
     const int rem = (int)(pix - (int64_t)n * H * W);
     const int y = rem / W, x = rem - y * W;
-    const u16* b = dy + (((int64_t)n * 2 * H + 2 * y) * Wo + 2 * x) * C + c8 * 8;
+    const u16* b = dy + (((int64_t)n * 2 * H + 2 * y) * Wo + 2 * x) * RE;
     float a0[8], a1[8], a2[8], a3[8];
-    unpack8<T>(*(const uint4*)b, a0);
-    unpack8<T>(*(const uint4*)(b + C), a1);
-    unpack8<T>(*(const uint4*)(b + (int64_t)Wo * C), a2);
-    unpack8<T>(*(const uint4*)(b + (int64_t)Wo * C + C), a3);
+    load8<T>(b, c8 * 8, C, a0);
+    load8<T>(b + RE, c8 * 8, C, a1);
+    load8<T>(b + (int64_t)Wo * RE, c8 * 8, C, a2);
+    load8<T>(b + (int64_t)Wo * RE + RE, c8 * 8, C, a3);
 #pragma unroll
     for (int e = 0; e < 8; ++e) a0[e] = (a0[e] + a1[e]) + (a2[e] + a3[e]);
-    *(uint4*)(dx + pix * C + c8 * 8) = pack8<T>(a0);
+    store8<T>(dx + pix * RE, c8 * 8, C, a0);
   }
 }
 
@@ -83,7 +116,7 @@ __device__ __forceinline__ void bilinear_adj_weights(int i, int n, float w[4]) {
 
 template <typename T>
 __global__ __launch_bounds__(256) void upsample_bilinear2_bwd_kernel(const u16* __restrict__ dy, u16* __restrict__ dx, int N, int H, int W, int C) {
-  const int C8 = C >> 3, Ho = 2 * H, Wo = 2 * W;
+  const int C8 = C >> 3, Ho = 2 * H, Wo = 2 * W, RE = row_elems<T>(C);
   const int64_t total = (int64_t)N * H * W * C8;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(i % C8);
@@ -105,13 +138,13 @@ __global__ __launch_bounds__(256) void upsample_bilinear2_bwd_kernel(const u16* 
         const int ox = 2 * x - 1 + b;
         if (wx[b] == 0.f) continue;
         float f[8];
-        unpack8<T>(*(const uint4*)(dy + (((int64_t)n * Ho + oy) * Wo + ox) * C + c8 * 8), f);
+        load8<T>(dy + (((int64_t)n * Ho + oy) * Wo + ox) * RE, c8 * 8, C, f);
         const float w = wy[a] * wx[b];
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] += w * f[e];
       }
     }
-    *(uint4*)(dx + pix * C + c8 * 8) = pack8<T>(acc);
+    store8<T>(dx + pix * RE, c8 * 8, C, acc);
   }
 }
 
@@ -129,14 +162,16 @@ __global__ __launch_bounds__(GT) void gn1_bwd_reduce_kernel(const u16* __restric
   const int n = blockIdx.y, p = blockIdx.x;
   const float* const gamma = gamma_ + (int64_t)n * gamma_ld;     // gamma_ld = 0: shared affine weight; > 0: per-sample (FiLM scale)
   const int C8 = C >> 3;
-  const int64_t n8 = hw * C8, base = (int64_t)n * hw * C;
+  const int RE = row_elems<T>(C);
+  const int64_t n8 = hw * C8, base = (int64_t)n * hw * RE;
   const int64_t per = (n8 + P - 1) / P, i0 = p * per, i1 = i0 + per < n8 ? i0 + per : n8;
   double s[4] = {0, 0, 0, 0};
   for (int64_t i = i0 + threadIdx.x; i < i1; i += GT) {
     const int c0 = (int)(i % C8) * 8;
     float xv[8], dv[8];
-    unpack8<T>(*(const uint4*)(x + base + i * 8), xv);
-    unpack8<T>(*(const uint4*)(dy + base + i * 8), dv);
+    const int64_t ro = base + (i / C8) * RE;
+    load8<T>(x + ro, c0, C, xv);
+    load8<T>(dy + ro, c0, C, dv);
     float q[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -183,22 +218,24 @@ __global__ __launch_bounds__(GT) void gn1_bwd_apply_kernel(const u16* __restrict
   __syncthreads();
   const float mu = coef[0], r = coef[1], m1 = coef[2], m2 = coef[3];
   const int C8 = C >> 3;
-  const int64_t n8 = hw * C8, base = (int64_t)n * hw * C;
+  const int RE = row_elems<T>(C);
+  const int64_t n8 = hw * C8, base = (int64_t)n * hw * RE;
   const int64_t per = (n8 + P - 1) / P, i0 = p * per, i1 = i0 + per < n8 ? i0 + per : n8;
   for (int64_t i = i0 + threadIdx.x; i < i1; i += GT) {
     const int c0 = (int)(i % C8) * 8;
     float xv[8], dv[8], o[8];
-    unpack8<T>(*(const uint4*)(x + base + i * 8), xv);
-    unpack8<T>(*(const uint4*)(dy + base + i * 8), dv);
+    const int64_t ro = base + (i / C8) * RE;
+    load8<T>(x + ro, c0, C, xv);
+    load8<T>(dy + ro, c0, C, dv);
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = r * ((gamma[c0 + e] + gamma_add) * dv[e] - m1 - (xv[e] - mu) * r * m2);
     if (res) {
       float rv[8];
-      unpack8<T>(*(const uint4*)(res + base + i * 8), rv);
+      load8<T>(res + ro, c0, C, rv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] += rv[e];
     }
-    *(uint4*)(dx + base + i * 8) = pack8<T>(o);
+    store8<T>(dx + ro, c0, C, o);
   }
 }
 
@@ -227,8 +264,9 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const u16* __restrict
     for (int c8 = my_c; c8 < C8; c8 += TPP) {
       const bool second = c8 * 8 >= C0;
       const int Cs = second ? C1 : C0, cl = second ? c8 * 8 - C0 : c8 * 8;
-      const u16* xb = (second ? x1 : x) + (int64_t)n * HW * Cs;
-      const u16* db = dy + (int64_t)n * HW * C;
+      const int REs = row_elems<T>(Cs), RE = row_elems<T>(C);
+      const u16* xb = (second ? x1 : x) + (int64_t)n * HW * REs;
+      const u16* db = dy + (int64_t)n * HW * RE;
       float a[8], b[8], sa[8], sb[8];
       *(float4*)a = *(const float4*)(ca + (int64_t)n * C + c8 * 8); *(float4*)(a + 4) = *(const float4*)(ca + (int64_t)n * C + c8 * 8 + 4);
       *(float4*)b = *(const float4*)(cb + (int64_t)n * C + c8 * 8); *(float4*)(b + 4) = *(const float4*)(cb + (int64_t)n * C + c8 * 8 + 4);
@@ -236,8 +274,8 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const u16* __restrict
       for (int e = 0; e < 8; ++e) { sa[e] = 0.f; sb[e] = 0.f; }
       for (int p = p0 + my_p; p < p1; p += PPI) {
         float f[8], d[8];
-        unpack8<T>(*(const uint4*)(xb + (int64_t)p * Cs + cl), f);
-        unpack8<T>(*(const uint4*)(db + (int64_t)p * C + c8 * 8), d);
+        load8<T>(xb + (int64_t)p * REs, cl, Cs, f);
+        load8<T>(db + (int64_t)p * RE, c8 * 8, C, d);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float dt = d[e] * act_grad(a[e] * f[e] + b[e], act);
@@ -313,10 +351,10 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const u16* __restrict
     const int n = (int)(pix / HW);
     const bool second = c8 * 8 >= C0;
     const int Cs = second ? C1 : C0, cl = second ? c8 * 8 - C0 : c8 * 8;
-    const int64_t off = pix * Cs + cl;
+    const int64_t off = pix * row_elems<T>(Cs);
     float f[8], d[8], a[8], b[8], pp[8], qq[8], o[8];
-    unpack8<T>(*(const uint4*)((second ? x1 : x) + off), f);
-    unpack8<T>(*(const uint4*)(dy + pix * C + c8 * 8), d);
+    load8<T>((second ? x1 : x) + off, cl, Cs, f);
+    load8<T>(dy + pix * row_elems<T>(C), c8 * 8, C, d);
     const int64_t co = (int64_t)n * C + c8 * 8;
     *(float4*)a = *(const float4*)(ca + co); *(float4*)(a + 4) = *(const float4*)(ca + co + 4);
     *(float4*)b = *(const float4*)(cb + co); *(float4*)(b + 4) = *(const float4*)(cb + co + 4);
@@ -327,11 +365,11 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const u16* __restrict
     const u16* ga = second ? gadd1 : gadd0;
     if (ga) {
       float r[8];
-      unpack8<T>(*(const uint4*)(ga + off), r);
+      load8<T>(ga + off, cl, Cs, r);
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] += r[e];
     }
-    *(uint4*)((second ? dx1 : dx0) + off) = pack8<T>(o);
+    store8<T>((second ? dx1 : dx0) + off, cl, Cs, o);
   }
 }
 }  // namespace
@@ -430,6 +468,76 @@ extern "C" int pmi_gn_bwd_apply(const void* x, const void* x1, int C0, const voi
   hipStream_t st = (hipStream_t)s;
   if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(gn_bwd_apply_kernel<BF16>, dim3(blocks), dim3(256), 0, st, (const u16*)x, (const u16*)x1, C0, (const u16*)dy, coef_a, coef_b, coef_p, coef_q, act, (const u16*)gadd0, (const u16*)gadd1, (u16*)dx0, (u16*)dx1, N, HW, C);
   else hipLaunchKernelGGL(gn_bwd_apply_kernel<F16>, dim3(blocks), dim3(256), 0, st, (const u16*)x, (const u16*)x1, C0, (const u16*)dy, coef_a, coef_b, coef_p, coef_q, act, (const u16*)gadd0, (const u16*)gadd1, (u16*)dx0, (u16*)dx1, N, HW, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+/* ---- the same adjoints over precise (hi + lo, PMI_DT_F16X2) tensors: [rows][C/G][hi G | lo G], C counts LOGICAL channels --------------------------- */
+static inline bool split_c_ok(int C) { return C > 0 && !(C & 7) && (C <= 32 || !(C & 31)); }
+#define SPLIT(KERN, G, B, ...) hipLaunchKernelGGL(KERN<F16X2>, G, B, 0, ST, __VA_ARGS__)
+
+extern "C" int pmi_split_add(const void* a, const void* b, void* out, int64_t rows, int C, pmi_stream_t s) {
+  if (!a || !b || !out || rows <= 0 || !split_c_ok(C)) return PMI_ERR_ARG;
+  hipLaunchKernelGGL(add_split_kernel, dim3(grid_for(rows * (C / 8))), dim3(256), 0, ST, (const u16*)a, (const u16*)b, (u16*)out, rows, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+extern "C" int pmi_split_relu_bwd(const void* g, const void* y, void* out, int64_t rows, int C, pmi_stream_t s) {
+  if (!g || !y || !out || rows <= 0 || !split_c_ok(C)) return PMI_ERR_ARG;
+  hipLaunchKernelGGL(relu_mask_split_kernel, dim3(grid_for(rows * (C / 8))), dim3(256), 0, ST, (const u16*)g, (const u16*)y, (u16*)out, rows, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+extern "C" int pmi_split_avgpool2_bwd(const void* dy, void* dx, int N, int H, int W, int C, pmi_stream_t s) {
+  if (!dy || !dx || N <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || !split_c_ok(C)) return PMI_ERR_ARG;
+  SPLIT(avgpool2_bwd_kernel, dim3(grid_for((int64_t)N * H * W * (C / 8))), dim3(256), (const u16*)dy, (u16*)dx, N, H, W, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+extern "C" int pmi_split_upsample_bilinear2_bwd(const void* dy, void* dx, int N, int H, int W, int C, pmi_stream_t s) {
+  if (!dy || !dx || N <= 0 || H <= 0 || W <= 0 || !split_c_ok(C)) return PMI_ERR_ARG;
+  SPLIT(upsample_bilinear2_bwd_kernel, dim3(grid_for((int64_t)N * H * W * (C / 8))), dim3(256), (const u16*)dy, (u16*)dx, N, H, W, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+extern "C" int pmi_split_upsample_nearest2_bwd(const void* dy, void* dx, int N, int H, int W, int C, pmi_stream_t s) {
+  if (!dy || !dx || N <= 0 || H <= 0 || W <= 0 || !split_c_ok(C)) return PMI_ERR_ARG;
+  SPLIT(upsample_nearest2_bwd_kernel, dim3(grid_for((int64_t)N * H * W * (C / 8))), dim3(256), (const u16*)dy, (u16*)dx, N, H, W, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+extern "C" int pmi_split_gn1_bwd(const void* x, const void* dy, const float* gamma, int gamma_ld, float gamma_add, const void* res, void* dx,
+                                 double* partial, int N, int64_t hw, int C, float eps, pmi_stream_t s) {
+  if (!x || !dy || !gamma || !dx || !partial || N <= 0 || hw <= 0 || !split_c_ok(C) || gamma_ld < 0) return PMI_ERR_ARG;
+  const int P = pmi_gn1_bwd_partials(hw, C);
+  SPLIT(gn1_bwd_reduce_kernel, dim3(P, N), dim3(GT), (const u16*)x, (const u16*)dy, gamma, gamma_ld, gamma_add, partial, hw, C, P);
+  PMI_CHECK_LAUNCH();
+  SPLIT(gn1_bwd_apply_kernel, dim3(P, N), dim3(GT), (const u16*)x, (const u16*)dy, gamma, gamma_ld, gamma_add, (const u16*)res, (u16*)dx,
+        partial, hw, C, P, eps);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+extern "C" int pmi_split_gn_bwd_stats(const void* x, const void* x1, int C0, const void* dy, const float* coef_a, const float* coef_b, int act,
+                                      float* ws, int N, int HW, int C, int nchunk, pmi_stream_t s) {
+  if (!x || !dy || !coef_a || !coef_b || !ws || N <= 0 || HW <= 0 || !split_c_ok(C) || !split_c_ok(C0) || C0 > C || (C0 < C && (!x1 || !split_c_ok(C - C0))) ||
+      nchunk <= 0)
+    return PMI_ERR_ARG;
+  const int C8 = C >> 3, TPP = C8 < 256 ? C8 : 256, PPI = 256 / TPP;
+  if (PPI * C > 4096) return PMI_ERR_ARG;
+  SPLIT(gn_bwd_stats_kernel, dim3(nchunk, N), dim3(256), (const u16*)x, (const u16*)x1, C0, (const u16*)dy, coef_a, coef_b, act, ws, HW, C, nchunk);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+extern "C" int pmi_split_gn_bwd_apply(const void* x, const void* x1, int C0, const void* dy, const float* coef_a, const float* coef_b,
+                                      const float* coef_p, const float* coef_q, int act, const void* gadd0, const void* gadd1, void* dx0, void* dx1,
+                                      int N, int HW, int C, pmi_stream_t s) {
+  if (!x || !dy || !coef_a || !coef_b || !coef_p || !coef_q || !dx0 || N <= 0 || HW <= 0 || !split_c_ok(C) || !split_c_ok(C0) || C0 > C ||
+      (C0 < C && (!x1 || !dx1 || !split_c_ok(C - C0))))
+    return PMI_ERR_ARG;
+  const int64_t total = (int64_t)N * HW * (C / 8);
+  const int blocks = (int)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
+  SPLIT(gn_bwd_apply_kernel, dim3(blocks), dim3(256), (const u16*)x, (const u16*)x1, C0, (const u16*)dy, coef_a, coef_b, coef_p, coef_q, act,
+        (const u16*)gadd0, (const u16*)gadd1, (u16*)dx0, (u16*)dx1, N, HW, C);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }

@@ -25,10 +25,18 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const pmi_gemm_f32_args a
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   for (int k0 = 0; k0 < a.K; k0 += TK) {
     // stage: 64 rows x 32 k of each operand, k fastest across threads (coalesced for row-major A and non-transposed B)
-    for (int e = tid; e < TM * TK; e += 256) {
-      const int r = e / TK, k = e - r * TK;
-      const int m = m0 + r, kk = k0 + k;
-      As[r * LDP + k] = (m < a.M && kk < a.K) ? A[(int64_t)m * a.lda + kk] : 0.f;
+    if (a.transA) {       // A[k][m]: m fastest across threads
+      for (int e = tid; e < TM * TK; e += 256) {
+        const int k = e / TM, r = e - k * TM;
+        const int m = m0 + r, kk = k0 + k;
+        As[r * LDP + k] = (m < a.M && kk < a.K) ? A[(int64_t)kk * a.lda + m] : 0.f;
+      }
+    } else {
+      for (int e = tid; e < TM * TK; e += 256) {
+        const int r = e / TK, k = e - r * TK;
+        const int m = m0 + r, kk = k0 + k;
+        As[r * LDP + k] = (m < a.M && kk < a.K) ? A[(int64_t)m * a.lda + kk] : 0.f;
+      }
     }
     if (a.transB) {       // B[k][n]: n fastest across threads
       for (int e = tid; e < TN * TK; e += 256) {
@@ -82,10 +90,25 @@ __global__ __launch_bounds__(256) void softmax_f32_kernel(float* __restrict__ S,
   for (int i = lane; i < T; i += 64) p[i] *= inv;
 }
 
+// in place: dP[row][0..T) <- scale * P o (dP - sum_s dP o P); one wave per row.  The row sum is a serial fp32 chain of T / 64 terms per lane, then
+// the wave butterfly
+__global__ __launch_bounds__(256) void softmax_bwd_f32_kernel(float* __restrict__ dP, const float* __restrict__ P, int rows, int T, int ld, float scale) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  float* d = dP + (int64_t)row * ld;
+  const float* p = P + (int64_t)row * ld;
+  float dot = 0.f;
+  for (int i = lane; i < T; i += 64) dot += d[i] * p[i];
+  dot = wave_sum(dot);
+  for (int i = lane; i < T; i += 64) d[i] = scale * (p[i] * (d[i] - dot));
+}
+
 }  // namespace
 
 extern "C" int pmi_gemm_f32(const pmi_gemm_f32_args* a, pmi_stream_t s) {
   if (!a || !a->A || !a->B || !a->D || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch <= 0 || a->batch_inner <= 0) return PMI_ERR_ARG;
+  // row pitches against the orientation: A is [M][K] (transA: [K][M]), B is [N][K] (transB: [K][N]), D is [M][N]
+  if (a->lda < (a->transA ? a->M : a->K) || a->ldb < (a->transB ? a->N : a->K) || a->ldd < a->N) return PMI_ERR_ARG;
   dim3 grid((a->N + TN - 1) / TN, (a->M + TM - 1) / TM, a->batch);
   hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, (hipStream_t)s, *a);
   PMI_CHECK_LAUNCH();
@@ -95,6 +118,13 @@ extern "C" int pmi_gemm_f32(const pmi_gemm_f32_args* a, pmi_stream_t s) {
 extern "C" int pmi_softmax_f32(float* S, int rows, int T, int ld, float scale, pmi_stream_t s) {
   if (!S || rows <= 0 || T <= 0 || ld < T) return PMI_ERR_ARG;
   hipLaunchKernelGGL(softmax_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)s, S, rows, T, ld, scale);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_softmax_bwd_f32(float* dP, const float* P, int rows, int T, int ld, float scale, pmi_stream_t s) {
+  if (!dP || !P || rows <= 0 || T <= 0 || ld < T) return PMI_ERR_ARG;
+  hipLaunchKernelGGL(softmax_bwd_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)s, dP, P, rows, T, ld, scale);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }

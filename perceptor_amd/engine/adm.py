@@ -318,9 +318,8 @@ class AdmEngine:
     # conv1 outputs, attention operands), 14.2 GB for GD "standard" at 512x512 x 8 of 288 GB -- and backward() walks the tape
     # once: no recomputation.  dX of a convolution is the forward kernel on transposed + flipped weights (ops.packed_dx); GroupNorm32 (+FiLM)
     # + SiLU backward is pmi_gn_bwd_*; attention backward is ops.self_attention_backward.
-    def _check_train(self):
-        if self.precise:
-            raise NotImplementedError("the ADM input gradient runs in the 16-bit modes (bf16 / f16)")
+    # precise mode walks the same tape over hi + lo tensors: the convolutions' dX on split-operand packings of the transposed weights, the
+    # memory-bound adjoints in their pmi_split_* forms, attention backward in exact fp32 (ops.attention_precise_backward).
 
     def _qkv_order1(self, l: _Attn, sd):
         """qkv projection producing channels (q|k|v, head, d) -- the layout of pmi_vit_attn_fwd / ops.attention_train -- whatever the
@@ -350,7 +349,7 @@ class AdmEngine:
             n, hh, ww, c = x.shape
             hp = torch.empty((n, hh // 2, ww // 2, c), dtype=x.dtype, device=x.device)
             skip = torch.empty_like(hp)
-            call("pmi_gn_apply_pool_skip", ptr(x), ptr(ca), ptr(cb), ptr(hp), ptr(skip), n, hh, ww, c, ACT_SILU, dt)
+            call("pmi_gn_apply_pool_skip", ptr(x), ptr(ca), ptr(cb), ptr(hp), ptr(skip), n, hh, ww, ops.logical_c(x, dt), ACT_SILU, dt)
             h = ops.igemm(hp, w[l.p + ".conv1"], nbias=nb, want_stats=True)
         else:
             h = ops.igemm(x, w[l.p + ".conv1"], a1=x1, up=l.up, nbias=nb, prologue=(ca, cb, ACT_SILU), want_stats=True)
@@ -372,7 +371,8 @@ class AdmEngine:
         g, b = w[l.p + ".gn"]
         ca, cb, parts = ops.group_norm_coeffs_train(x, g, b, 32, dt)
         hn = torch.empty_like(x)
-        call("pmi_gn_apply", ptr(x), None, c, ptr(ca), ptr(cb), None, ptr(hn), n, hh, ww, c, ACT_NONE, 0, dt)
+        cl = ops.logical_c(x, dt)
+        call("pmi_gn_apply", ptr(x), None, cl, ptr(ca), ptr(cb), None, ptr(hn), n, hh, ww, cl, ACT_NONE, 0, dt)
         lin, _ = self._qkv_order1(l, sd)
         a, saved = ops.self_attention_train(ops.igemm(hn.view(n * t, c), lin), n, t, l.heads, dt)
         out = ops.igemm(a, w[l.p + ".proj"], residual=x.view(n * t, c), want_stats=True, hw=t)
@@ -400,7 +400,6 @@ class AdmEngine:
     @torch.no_grad()
     def forward_train(self, images: torch.Tensor, timesteps: torch.Tensor, state_dict, out_channels: Optional[int] = None):
         """As forward(), keeping what backward() needs.  Returns (model output NCHW fp32, tape)."""
-        self._check_train()
         emb, h = self._embed_input(images, timesteps)
         sd = state_dict
         tape = {"inp": [], "mid": [], "out": []}
@@ -439,7 +438,7 @@ class AdmEngine:
             if x1 is None:
                 gs0, gs1 = ops.igemm(g, ops.packed_dx(w, p + ".skipT", skw, dt, dev)), None
             else:
-                c0 = x.shape[-1]
+                c0 = ops.logical_c(x, dt)
                 gs0 = ops.igemm(g, ops.packed_dx(w, p + ".skipT0", skw[:, :c0], dt, dev))
                 gs1 = ops.igemm(g, ops.packed_dx(w, p + ".skipT1", skw[:, c0:], dt, dev))
         else:
@@ -484,9 +483,8 @@ class AdmEngine:
     @torch.no_grad()
     def backward(self, tape, d_out: torch.Tensor, state_dict) -> torch.Tensor:
         """d loss / d images (NCHW fp32, images in [0, 1]) from d loss / d output (NCHW fp32, the first d_out.shape[1] output channels) and the
-        tape of forward_train().  f16 engines scale the gradient by a power of two on the way in and back on the way out
+        tape of forward_train().  f16 and precise engines scale the gradient by a power of two on the way in and back on the way out
         (ops.grad_to_nhwc); bf16 needs no scaling."""
-        self._check_train()
         dt = self.dt
         sd = {k: v.detach() for k, v in state_dict.items()}
         g, scale = ops.grad_to_nhwc(d_out, dt, self.device)                                     # output channels + padding
@@ -502,7 +500,6 @@ class AdmEngine:
         # the out blocks popped hs from the end: the LAST out list read hs[0]; walking them reversed gives g_hs = [for hs[0], hs[1], ...]
         for i in range(len(tape["inp"]) - 1, -1, -1):
             gk = g_hs[i]
-            tot = torch.empty_like(g)
-            call("pmi_add16", ptr(g), ptr(gk), ptr(tot), g.numel(), dt)                         # hs[i] feeds the next block AND an out block
+            tot = ops.add2(g, gk, dt)                                                      # hs[i] feeds the next block AND an out block
             g, _ = self._back(tape["inp"][i], tot, sd, ld)
         return ops.grad_to_nchw(g, 3, 2.0 / scale)                                              # x = 2 * images - 1

@@ -72,6 +72,13 @@ class AdmMixedEngine(AdmEngine):
     shipped config, otherwise every convolution at 1/4 resolution and below); plain_from: levels (down-sampling factor) that run the plain
     f16 blocks."""
 
+    def forward_train(self, *args, **kwargs):
+        raise NotImplementedError("the mixed mode has no input gradient of its own (plain-f16 deep levels, per-layer single / doubled operands, "
+                                  "split <-> plain level boundaries): use an f16 or a precise engine")
+
+    def backward(self, *args, **kwargs):
+        raise NotImplementedError("the mixed mode has no input gradient of its own: use an f16 or a precise engine")
+
     def __init__(self, cfg: AdmConfig, state_dict: Dict[str, torch.Tensor], device, single=None, plain_from: int = 32):
         self.cfg, self.device = cfg, torch.device(device)
         self.dt, self.precise = DT_F16X2, True

@@ -242,15 +242,16 @@ def f16_grad_scale(amax) -> float:
 
 def grad_to_nhwc(d_out: torch.Tensor, dt: int, device, cpad: int = 8, mul: float = 1.0):
     """d loss / d output (NCHW fp32, any device) -> (NHWC 16-bit [N, H, W, cpad] = d_out * mul * scale, scale).  f16 scales by
-    f16_grad_scale (image gradients of a CLIP loss are ~1e-6 and would flush to zero in f16); bf16 needs no scaling."""
+    f16_grad_scale (image gradients of a CLIP loss are ~1e-6 and would flush to zero in f16); bf16 needs no scaling.  precise: a split
+    [N, H, W, 2 cpad] tensor with the same scale -- hi + lo has f16's exponent range, and keeps its ~22 bits only while lo is a normal f16."""
     d = d_out.to(device=device, dtype=torch.float32).contiguous()
     n, c, h, w = d.shape
     scale = 1.0
-    if dt == _hip.DT_F16:
+    if dt in (_hip.DT_F16, DT_F16X2):
         amax = _empty((n,), torch.float32, device)
         call("pmi_quantile_abs", ptr(d), ptr(amax), n, c * h * w, 1.0)
         scale = f16_grad_scale(amax.tolist())
-    g = _empty((n, h, w, cpad), _hip.TORCH_DTYPE[dt], device)
+    g = _empty((n, h, w, 2 * cpad if dt == DT_F16X2 else cpad), _hip.TORCH_DTYPE[dt], device)
     call("pmi_nchw_to_nhwc", ptr(d), ptr(g), n, c, h, w, cpad, mul * scale, 0.0, dt)
     return g, scale
 
@@ -260,6 +261,17 @@ def grad_to_nchw(g: torch.Tensor, c: int, mul: float) -> torch.Tensor:
     n, h, w, _ = g.shape
     out = _empty((n, c, h, w), torch.float32, g.device)
     call("pmi_nhwc_to_nchw", ptr(g), g.shape[-1], ptr(out), n, h, w, c, mul, 0.0)
+    return out
+
+
+def add2(a: torch.Tensor, b: torch.Tensor, dt: int) -> torch.Tensor:
+    """a + b of two activation-shaped tensors (two gradients of a value consumed twice, main + skip of a block); precise: the sum of the two
+    hi + lo values in fp32, split again."""
+    out = torch.empty_like(a)
+    if dt == DT_F16X2:
+        call("pmi_split_add", ptr(a), ptr(b), ptr(out), a.numel() // a.shape[-1], a.shape[-1] // 2)
+    else:
+        call("pmi_add16", ptr(a), ptr(b), ptr(out), a.numel(), dt)
     return out
 
 
@@ -611,20 +623,29 @@ def group_norm_backward(x: torch.Tensor, dy: torch.Tensor, ca, cb, parts, gamma,
     """Gradient wrt x (and x1) of y = act(GroupNorm(cat(x, x1)) * gamma [FiLM] + beta) given dy = d loss / d y [N, H, W, C] (one tensor over the
     concat) -- pmi_gn_bwd_stats / _finalize / _apply; gadd0 / gadd1: gradients arriving over another path, added on the way out.
     Returns (dx, dx1)."""
-    n, h, w, c0 = x.shape
-    c1 = x1.shape[-1] if x1 is not None else 0
+    n, h, w, _ = x.shape
+    c0 = logical_c(x, dt)
+    c1 = logical_c(x1, dt) if x1 is not None else 0
     c, hw, dev = c0 + c1, h * w, x.device
-    assert dy.shape[-1] == c and dy.is_contiguous() and x.is_contiguous() and (x1 is None or x1.is_contiguous())
+    split = dt == DT_F16X2
+    assert logical_c(dy, dt) == c and dy.is_contiguous() and x.is_contiguous() and (x1 is None or x1.is_contiguous())
     nchunk = max(1, min(hw // 8, (1024 + n - 1) // n))
     wsb = _empty((n, nchunk, c, 2), torch.float32, dev)
-    call("pmi_gn_bwd_stats", ptr(x), ptr(x1), c0, ptr(dy), ptr(ca), ptr(cb), act, ptr(wsb), n, hw, c, nchunk, dt)
+    if split:
+        call("pmi_split_gn_bwd_stats", ptr(x), ptr(x1), c0, ptr(dy), ptr(ca), ptr(cb), act, ptr(wsb), n, hw, c, nchunk)
+    else:
+        call("pmi_gn_bwd_stats", ptr(x), ptr(x1), c0, ptr(dy), ptr(ca), ptr(cb), act, ptr(wsb), n, hw, c, nchunk, dt)
     cp, cq = _empty((n, c), torch.float32, dev), _empty((n, c), torch.float32, dev)
     call("pmi_gn_bwd_finalize", ptr(parts[0]), parts[1], parts[2], ptr(parts[3]), parts[4], parts[5], ptr(wsb), nchunk, ptr(gamma), ptr(film), film_ld,
          ptr(cp), ptr(cq), n, hw, groups, eps)
     dx0 = torch.empty_like(x)
     dx1 = torch.empty_like(x1) if x1 is not None else None
-    call("pmi_gn_bwd_apply", ptr(x), ptr(x1), c0, ptr(dy), ptr(ca), ptr(cb), ptr(cp), ptr(cq), act, ptr(gadd0), ptr(gadd1), ptr(dx0), ptr(dx1),
-         n, hw, c, dt)
+    if split:
+        call("pmi_split_gn_bwd_apply", ptr(x), ptr(x1), c0, ptr(dy), ptr(ca), ptr(cb), ptr(cp), ptr(cq), act, ptr(gadd0), ptr(gadd1), ptr(dx0),
+             ptr(dx1), n, hw, c)
+    else:
+        call("pmi_gn_bwd_apply", ptr(x), ptr(x1), c0, ptr(dy), ptr(ca), ptr(cb), ptr(cp), ptr(cq), act, ptr(gadd0), ptr(gadd1), ptr(dx0), ptr(dx1),
+             n, hw, c, dt)
     return dx0, dx1
 
 
@@ -684,25 +705,31 @@ def avgpool2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
     """Adjoint of avgpool2: a quarter of each gradient value to each pixel of its 2x2 block, [N, H, W, C] -> [N, 2H, 2W, C]."""
     n, h, w, c = g.shape
     out = _empty((n, 2 * h, 2 * w, c), g.dtype, g.device)
-    call("pmi_avgpool2_bwd", ptr(g), ptr(out), n, 2 * h, 2 * w, c, dt)
+    if dt == DT_F16X2:
+        call("pmi_split_avgpool2_bwd", ptr(g), ptr(out), n, 2 * h, 2 * w, c // 2)
+    else:
+        call("pmi_avgpool2_bwd", ptr(g), ptr(out), n, 2 * h, 2 * w, c, dt)
     return out
 
 
-def _up2_bwd(fn: str, g: torch.Tensor, dt: int) -> torch.Tensor:
+def _up2_bwd(fn: str, fn_split: str, g: torch.Tensor, dt: int) -> torch.Tensor:
     n, h, w, c = g.shape
     out = _empty((n, h // 2, w // 2, c), g.dtype, g.device)
-    call(fn, ptr(g), ptr(out), n, h // 2, w // 2, c, dt)
+    if dt == DT_F16X2:
+        call(fn_split, ptr(g), ptr(out), n, h // 2, w // 2, c // 2)
+    else:
+        call(fn, ptr(g), ptr(out), n, h // 2, w // 2, c, dt)
     return out
 
 
 def upsample_nearest2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
     """Adjoint of upsample_nearest2: the sum of each 2x2 block, [N, 2H, 2W, C] -> [N, H, W, C]."""
-    return _up2_bwd("pmi_upsample_nearest2_bwd", g, dt)
+    return _up2_bwd("pmi_upsample_nearest2_bwd", "pmi_split_upsample_nearest2_bwd", g, dt)
 
 
 def upsample_bilinear2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
     """Adjoint of upsample_bilinear2, [N, 2H, 2W, C] -> [N, H, W, C]."""
-    return _up2_bwd("pmi_upsample_bilinear2_bwd", g, dt)
+    return _up2_bwd("pmi_upsample_bilinear2_bwd", "pmi_split_upsample_bilinear2_bwd", g, dt)
 
 
 def attention(qkv: torch.Tensor, heads: int, order: int, dt: int, causal: bool = False) -> torch.Tensor:
@@ -849,6 +876,8 @@ def attention_backward(qkv: torch.Tensor, p: torch.Tensor, d_out: torch.Tensor, 
 def self_attention_train(qkv: torch.Tensor, n: int, t: int, heads: int, dt: int):
     """Self-attention keeping what self_attention_backward needs: qkv [N*T, 3C] 16-bit, channels (q|k|v, head, d) -> (out [N*T, C], saved).
     64-channel heads run the flash-style forward that keeps the log-sum-exp (csrc/attn.hip), other head dims attention_train."""
+    if dt == DT_F16X2:
+        return attention_precise_train(qkv, n, t, heads)
     c = qkv.shape[-1] // 3
     if c // heads == 64:
         tp32 = (t + 31) // 32 * 32
@@ -863,6 +892,8 @@ def self_attention_train(qkv: torch.Tensor, n: int, t: int, heads: int, dt: int)
 
 def self_attention_backward(saved, da: torch.Tensor, n: int, t: int, heads: int, dt: int) -> torch.Tensor:
     """d loss / d qkv [N*T, 3C] from d loss / d out [N*T, C] and self_attention_train's `saved`."""
+    if dt == DT_F16X2:
+        return attention_precise_backward(saved, da, n, t, heads)
     c = da.shape[-1]
     if c // heads == 64:
         aws, lse, a = saved
@@ -877,13 +908,16 @@ def self_attention_backward(saved, da: torch.Tensor, n: int, t: int, heads: int,
 
 
 def gemm_f32(A: torch.Tensor, B: torch.Tensor, D: torch.Tensor, *, M: int, N: int, K: int, lda: int, ldb: int, ldd: int, trans_b: bool = False,
+             trans_a: bool = False,
              bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, alpha: float = 1.0, batch: int = 1, batch_inner: int = 1,
              sA=(0, 0), sB=(0, 0), sD=(0, 0), a_off: int = 0, b_off: int = 0, d_off: int = 0, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Exact-fp32 batched GEMM on the f32-input MFMA (csrc/f32gemm.hip): D[z] = act(alpha * A[z] @ B[z]^T + bias)."""
+    """Exact-fp32 batched GEMM on the f32-input MFMA (csrc/f32gemm.hip): D[z] = act(alpha * A[z] @ B[z]^T + bias); trans_b: B[z] is [K, N],
+    trans_a: A[z] is [K, M]."""
     a = _hip.GemmF32Args()
     a.A, a.B, a.bias, a.D = A.data_ptr() + 4 * a_off, B.data_ptr() + 4 * b_off, ptr(bias), D.data_ptr() + 4 * d_off
     a.M, a.N, a.K, a.lda, a.ldb, a.ldd = M, N, K, lda, ldb, ldd
     a.transB, a.act, a.alpha, a.batch, a.batch_inner = int(trans_b), act, alpha, batch, batch_inner
+    a.transA = int(trans_a)
     a.sA_o, a.sA_i = sA
     a.sB_o, a.sB_i = sB
     a.sD_o, a.sD_i = sD
@@ -925,3 +959,51 @@ def attention_precise(qkv: torch.Tensor, heads: int, order: int) -> torch.Tensor
     out = _empty((n, t, 2 * c), torch.float16, dev)
     call("pmi_split_from_f32", ptr(o32), c, ptr(out), n * t, c)
     return out
+
+
+def attention_precise_train(qkv: torch.Tensor, n: int, t: int, heads: int):
+    """self_attention_train in precise mode: qkv is a precise [N*T, 2*3C] tensor, channels (q|k|v, head, d) -> (precise out [N*T, 2C], saved).
+    The same three launches as attention_precise (order 1); the fp32 copy of q, k, v and the fp32 softmax P stay on the tape."""
+    c3 = qkv.shape[-1] // 2
+    c = c3 // 3
+    d = c // heads
+    dev = qkv.device
+    q32 = _empty((n, t, c3), torch.float32, dev)
+    call("pmi_split_to_f32", ptr(qkv), ptr(q32), n * t, c3)
+    p = _empty((n * heads, t, t), torch.float32, dev)
+    gemm_f32(q32, q32, p, M=t, N=t, K=d, lda=c3, ldb=c3, ldd=t, batch=n * heads, batch_inner=heads,
+             sA=(t * c3, d), sB=(t * c3, d), sD=(heads * t * t, t * t), b_off=c)
+    call("pmi_softmax_f32", ptr(p), n * heads * t, t, t, float(d) ** -0.5)
+    o32 = _empty((n, t, c), torch.float32, dev)
+    gemm_f32(p, q32, o32, M=t, N=d, K=t, lda=t, ldb=c3, ldd=c, trans_b=True, batch=n * heads, batch_inner=heads,
+             sA=(heads * t * t, t * t), sB=(t * c3, d), sD=(t * c, d), b_off=2 * c)
+    out = _empty((n * t, 2 * c), torch.float16, dev)
+    call("pmi_split_from_f32", ptr(o32), c, ptr(out), n * t, c)
+    return out, (q32, p)
+
+
+def attention_precise_backward(saved, da: torch.Tensor, n: int, t: int, heads: int) -> torch.Tensor:
+    """Precise d loss / d qkv [N*T, 2*3C], channels (q|k|v, head, d), from the precise d loss / d out [N*T, 2C]: the five products of
+    attention_backward in exact fp32 (pmi_gemm_f32), dS = scale P o (dP - rowsum(dP o P)) in place over dP (pmi_softmax_bwd_f32)."""
+    q32, p = saved
+    c3 = q32.shape[-1]
+    c = c3 // 3
+    d = c // heads
+    dev = da.device
+    nh = n * heads
+    do32 = _empty((n, t, c), torch.float32, dev)
+    call("pmi_split_to_f32", ptr(da), ptr(do32), n * t, c)
+    sP, sQ, sO = (heads * t * t, t * t), (t * c3, d), (t * c, d)
+    ds = _empty((nh, t, t), torch.float32, dev)
+    gemm_f32(do32, q32, ds, M=t, N=t, K=d, lda=c, ldb=c3, ldd=t, batch=nh, batch_inner=heads, sA=sO, sB=sQ, sD=sP, b_off=2 * c)     # dP = dO V^T
+    call("pmi_softmax_bwd_f32", ptr(ds), ptr(p), nh * t, t, t, float(d) ** -0.5)
+    dq32 = _empty((n, t, c3), torch.float32, dev)
+    gemm_f32(p, do32, dq32, M=t, N=d, K=t, lda=t, ldb=c, ldd=c3, trans_a=True, trans_b=True, batch=nh, batch_inner=heads,
+             sA=sP, sB=sO, sD=sQ, d_off=2 * c)                                                                                  # dV = P^T dO
+    gemm_f32(ds, q32, dq32, M=t, N=d, K=t, lda=t, ldb=c3, ldd=c3, trans_b=True, batch=nh, batch_inner=heads,
+             sA=sP, sB=sQ, sD=sQ, b_off=c)                                                                                      # dQ = dS K
+    gemm_f32(ds, q32, dq32, M=t, N=d, K=t, lda=t, ldb=c3, ldd=c3, trans_a=True, trans_b=True, batch=nh, batch_inner=heads,
+             sA=sP, sB=sQ, sD=sQ, d_off=c)                                                                                      # dK = dS^T Q
+    dqkv = _empty((n * t, 2 * c3), torch.float16, dev)
+    call("pmi_split_from_f32", ptr(dq32), c3, ptr(dqkv), n * t, c3)
+    return dqkv

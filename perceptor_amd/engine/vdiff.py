@@ -325,10 +325,8 @@ class VDiffEngine:
     # denoised image to the noise: d loss / d images through the UNet, weights frozen.  forward_train() runs the same kernels as
     # forward() but keeps, per block, the tensors a backward needs (the post-ReLU outputs double as ReLU masks); backward() walks the
     # tape in reverse.  dX of a convolution is the forward convolution on transposed + flipped weights (packed lazily, once), so the
-    # MFMA kernels, their fused residual add and the fragment-ordered weight paths are reused unchanged.
-    def _check_backward_support(self):
-        if self.precise:
-            raise NotImplementedError("input gradient runs in the 16-bit modes (bf16 / f16)")
+    # MFMA kernels, their fused residual add and the fragment-ordered weight paths are reused unchanged.  precise mode walks the same tape
+    # over hi + lo tensors (split-operand packings of the transposed weights, the pmi_split_* adjoints, exact-fp32 attention backward).
 
     def _res_train_cond(self, l: Res, p, x, x1, mod, tape):
         """cc12m_1.py:46-61: conv -> GroupNorm(1, C, affine=False) -> Modulation2d -> ReLU -> conv [-> the same again] + skip, with the
@@ -338,7 +336,7 @@ class VDiffEngine:
         h = ops.igemm(x, w[p + ".c1"], a1=x1)
         hn = ops.group_norm(h, None, None, 1, dt, film=mod[:, l.mod1:], film_ld=ld, act=ACT_RELU)
         if l.last:
-            skip = ops.igemm(x, w[p + ".skip"], a1=x1)
+            skip = ops.igemm(x, w[p + ".skip"], a1=x1, out_f32=self.precise)      # (precise: a 4-channel row cannot hold hi + lo groups)
             y = ops.igemm(hn, w[p + ".c2"], residual=skip, out_f32=True)
             h2 = r2 = None
         else:
@@ -347,8 +345,7 @@ class VDiffEngine:
             if l.cin != l.cout:
                 y = ops.igemm(x, w[p + ".skip"], a1=x1, residual=r2)
             else:
-                y = torch.empty_like(r2)
-                call("pmi_add16", ptr(r2), ptr(x), ptr(y), r2.numel(), dt)
+                y = ops.add2(r2, x, dt)
         tape.append(("res", l, p, hn, r2, x1 is not None, h, h2, mod))
         return y
 
@@ -358,7 +355,7 @@ class VDiffEngine:
         dt, w = self.dt, self.w
         h1 = ops.igemm(x, w[p + ".c1"], a1=x1, act=ACT_RELU)
         if l.last:
-            skip = ops.igemm(x, w[p + ".skip"], a1=x1)
+            skip = ops.igemm(x, w[p + ".skip"], a1=x1, out_f32=self.precise)      # (precise: a 4-channel row cannot hold hi + lo groups)
             y = ops.igemm(h1, w[p + ".c2"], residual=skip, out_f32=True)
             r2 = None
         else:
@@ -366,15 +363,14 @@ class VDiffEngine:
             if l.cin != l.cout:
                 y = ops.igemm(x, w[p + ".skip"], a1=x1, residual=r2)
             else:
-                y = torch.empty_like(r2)
-                call("pmi_add16", ptr(r2), ptr(x), ptr(y), r2.numel(), dt)
+                y = ops.add2(r2, x, dt)
         tape.append(("res", l, p, h1, r2, x1 is not None, None, None, None))
         return y
 
     def _attn_train(self, l: Attn, p, x, tape):
         dt, w = self.dt, self.w
         n, hh, ww, c = x.shape
-        t, heads = hh * ww, c // self.spec.get("head_dim", 64)
+        t, heads = hh * ww, ops.logical_c(x, dt) // self.spec.get("head_dim", 64)
         hn = x
         if self.spec.get("attn_norm", True):
             g, b = w[p + ".gn"]
@@ -410,7 +406,6 @@ class VDiffEngine:
     @torch.no_grad()
     def forward_train(self, images: torch.Tensor, t: torch.Tensor, clip_embed: Optional[torch.Tensor] = None):
         """As forward(), keeping what backward() needs.  Returns (v NCHW fp32, tape)."""
-        self._check_backward_support()
         mod, x = self._embed_input(images, t, clip_embed)
         tape = []
         y = self._run_train(self.spec["net"], "net", x, tape, mod)
@@ -418,19 +413,26 @@ class VDiffEngine:
 
     def _mask(self, g, y):
         """g * (y > 0) in place: y is a post-ReLU tensor, its sign is the mask."""
-        call("pmi_act_bwd", ptr(g), ptr(y), ptr(g), g.numel(), ACT_RELU, self.dt)
+        if self.precise:        # the sign of hi + lo, not of each half
+            call("pmi_split_relu_bwd", ptr(g), ptr(y), ptr(g), g.numel() // g.shape[-1], g.shape[-1] // 2)
+        else:
+            call("pmi_act_bwd", ptr(g), ptr(y), ptr(g), g.numel(), ACT_RELU, self.dt)
         return g
 
     def _film_norm_back(self, xpre, d, mod, off, d_mod):
         """d (gradient wrt Modulation2d's output, ReLU mask already applied) -> gradient wrt the GroupNorm(1, C) input xpre; adds this
         layer's d scale | d shift into d_mod unless it is None."""
-        n, hh, ww, c = xpre.shape
+        n, hh, ww, _ = xpre.shape
+        c = ops.logical_c(xpre, self.dt)
         if d_mod is not None:
             self._cond_grad_layer(xpre, d, off, d_mod)
         out = torch.empty_like(xpre)
         scale = mod[:, off:]                                                     # [N, >= C] view: (scale | shift) of this layer
         part = torch.empty((n, _hip.lib().pmi_gn1_bwd_partials(hh * ww, c), 4), dtype=torch.float64, device=xpre.device)
-        call("pmi_gn1_bwd", ptr(xpre), ptr(d), scale.data_ptr(), mod.stride(0), 1.0, None, ptr(out), ptr(part), n, hh * ww, c, 1e-5, self.dt)
+        if self.precise:
+            call("pmi_split_gn1_bwd", ptr(xpre), ptr(d), scale.data_ptr(), mod.stride(0), 1.0, None, ptr(out), ptr(part), n, hh * ww, c, 1e-5)
+        else:
+            call("pmi_gn1_bwd", ptr(xpre), ptr(d), scale.data_ptr(), mod.stride(0), 1.0, None, ptr(out), ptr(part), n, hh * ww, c, 1e-5, self.dt)
         return out
 
     # ---- gradient to the conditioning (cc12m_1: upstream velocity_diffusion.py:96-109 lets autograd reach `conditioning`) -----------------
@@ -439,8 +441,9 @@ class VDiffEngine:
     # (pmi_gn_bwd_stats), the per-sample moments come from the forward statistics pass; all layers accumulate into one [N, sum 2C] row that
     # goes back through the mapping network (four tiny fp32 GEMMs on the exact-fp32 MFMA, recomputed forward for the ReLU masks).
     def _cond_grad_layer(self, xpre, d, off, d_mod):
-        n, hh, ww, c = xpre.shape
+        n, hh, ww, _ = xpre.shape
         hw, dev, dt = hh * ww, xpre.device, self.dt
+        c = ops.logical_c(xpre, dt)
         nchunk = max(1, min(hw // 8, (1024 + n - 1) // n))
         ws = torch.empty((n, nchunk, c, 2), dtype=torch.float32, device=dev)
         call("pmi_gn_stats", ptr(xpre), None, c, ptr(ws), n, hw, c, 1, nchunk, dt)
@@ -451,7 +454,10 @@ class VDiffEngine:
         one = torch.ones((n, c), dtype=torch.float32, device=dev)
         zero = torch.zeros((n, c), dtype=torch.float32, device=dev)
         wb = torch.empty((n, nchunk, c, 2), dtype=torch.float32, device=dev)
-        call("pmi_gn_bwd_stats", ptr(xpre), None, c, ptr(d), ptr(one), ptr(zero), ACT_NONE, ptr(wb), n, hw, c, nchunk, dt)
+        if self.precise:
+            call("pmi_split_gn_bwd_stats", ptr(xpre), None, c, ptr(d), ptr(one), ptr(zero), ACT_NONE, ptr(wb), n, hw, c, nchunk)
+        else:
+            call("pmi_gn_bwd_stats", ptr(xpre), None, c, ptr(d), ptr(one), ptr(zero), ACT_NONE, ptr(wb), n, hw, c, nchunk, dt)
         ab = wb.double().sum(dim=1)                                        # [n, c, 2]: sum_p d, sum_p d x
         d_mod[:, off:off + c] += (r[:, None] * (ab[..., 1] - mu[:, None] * ab[..., 0])).float()
         d_mod[:, off + c:off + 2 * c] += ab[..., 0].float()
@@ -513,7 +519,8 @@ class VDiffEngine:
         skw = sd[p + ".skip.weight"] if has_skip else None
         spad = 8 if l.last else None
         if not two:
-            gs = ops.igemm(g, ops.packed_dx(w, p + ".skipT", skw, dt, dev, cin_pad=spad)) if has_skip else g
+            # (precise, first block: its 19 + 1 gradient channels cannot hold hi + lo groups -- the skip's dX stays fp32 like conv1's)
+            gs = ops.igemm(g, ops.packed_dx(w, p + ".skipT", skw, dt, dev, cin_pad=spad), out_f32=first and self.precise) if has_skip else g
             return ops.igemm(dh1, ops.packed_dx(w, p + ".c1T", w1, dt, dev), residual=gs, out_f32=first), None
         half = l.cin // 2                                                        # conv1 / skip read cat([main(x), x]): one dX per source
         outs = []
@@ -527,17 +534,20 @@ class VDiffEngine:
         _, l, p, x, saved = rec
         dt = self.dt
         n, hh, ww, c = x.shape
-        t, heads = hh * ww, c // self.spec.get("head_dim", 64)
+        cl = ops.logical_c(x, dt)
+        t, heads = hh * ww, cl // self.spec.get("head_dim", 64)
         g2 = g.reshape(n * t, c)
         da = ops.igemm(g2, ops.packed_dx(self.w, p + ".outT", sd[p + ".out_proj.weight"], dt, self.device))
         dqkv = ops.self_attention_backward(saved, da, n, t, heads, dt)
         dhn = ops.igemm(dqkv, ops.packed_dx(self.w, p + ".qkvT", sd[p + ".qkv_proj.weight"], dt, self.device))
+        if not self.spec.get("attn_norm", True):     # no norm in front of the projections: the two paths just add
+            return ops.add2(dhn, g2, dt).view(x.shape)
         gx = torch.empty_like(x)
-        if self.spec.get("attn_norm", True):
-            part = torch.empty((n, _hip.lib().pmi_gn1_bwd_partials(t, c), 4), dtype=torch.float64, device=x.device)
-            call("pmi_gn1_bwd", ptr(x), ptr(dhn), ptr(self.w[p + ".gn"][0]), 0, 0.0, ptr(g2), ptr(gx), ptr(part), n, t, c, 1e-5, dt)
-        else:                                        # no norm in front of the projections: the two paths just add
-            call("pmi_add16", ptr(dhn), ptr(g2), ptr(gx), gx.numel(), dt)
+        part = torch.empty((n, _hip.lib().pmi_gn1_bwd_partials(t, cl), 4), dtype=torch.float64, device=x.device)
+        if self.precise:
+            call("pmi_split_gn1_bwd", ptr(x), ptr(dhn), ptr(self.w[p + ".gn"][0]), 0, 0.0, ptr(g2), ptr(gx), ptr(part), n, t, cl, 1e-5)
+        else:
+            call("pmi_gn1_bwd", ptr(x), ptr(dhn), ptr(self.w[p + ".gn"][0]), 0, 0.0, ptr(g2), ptr(gx), ptr(part), n, t, cl, 1e-5, dt)
         return gx
 
     def _back(self, tape, g, sd, d_mod, outermost=False):
@@ -554,9 +564,7 @@ class VDiffEngine:
                 assert g1 is not None, "a SkipBlock is always followed by the block that reads its concat"
                 g_inner, g_x = (g1, g) if self.spec.get("skip_first") else (g, g1)
                 gm = self._back(rec[1], g_inner, sd, d_mod)                      # through main(x)
-                out = torch.empty_like(gm)
-                call("pmi_add16", ptr(gm), ptr(g_x), ptr(out), gm.numel(), self.dt)
-                g, g1 = out, None
+                g, g1 = ops.add2(gm, g_x, self.dt), None
             else:
                 assert g1 is None
                 if kind == "attn":
@@ -573,9 +581,8 @@ class VDiffEngine:
     def backward(self, tape, d_v: torch.Tensor, state_dict, cond_grad=None):
         """d loss / d images (NCHW fp32, images in [0, 1]) from d loss / d v (NCHW fp32 [N, 3, H, W]) and the tape of forward_train().
         `state_dict`: the model's parameters (reference key names) -- the transposed weight packings are built from it on first use.
-        f16 engines scale the gradient by a power of two on the way in and back on the way out (ops.grad_to_nhwc); bf16 needs no scaling.
+        f16 and precise engines scale the gradient by a power of two on the way in and back on the way out (ops.grad_to_nhwc); bf16 needs no scaling.
         cond_grad = (t [N], clip_embed [N, D]) of a conditioned net: also returns d loss / d clip_embed -> (d_images, d_clip_embed)."""
-        self._check_backward_support()
         dev, n = self.device, d_v.shape[0]
         d_mod = None
         if cond_grad is not None:

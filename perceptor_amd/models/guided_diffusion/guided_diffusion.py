@@ -44,7 +44,7 @@ class _PredictedNoise(torch.autograd.Function):
     def forward(ctx, diffused, idx, model):
         eng = model.grad_engine
         eps, tape = eng.forward_train(diffused, idx, model.model.state_dict(), out_channels=3)
-        if eng is not model.engine:          # mixed / precise model: the VALUE is that mode's, the tape (and so the gradient) the f16 engine's
+        if eng is not model.engine:          # mixed / precise model with grad_mode "f16": the VALUE is that mode's, the tape (and so the gradient) the f16 engine's
             eps = model.engine.forward(diffused, idx, out_channels=3)
         ctx.model, ctx.tape = model, tape
         return eps
@@ -57,12 +57,20 @@ class _PredictedNoise(torch.autograd.Function):
 
 class GuidedDiffusion(torch.nn.Module):
     def __init__(self, name="standard", *, weights="synthetic", checkpoint: Optional[str] = None, dtype="bf16", seed=0,
-                 config: Optional[adm.AdmConfig] = None):
+                 config: Optional[adm.AdmConfig] = None, grad_mode: str = "f16"):
         """
         Args:
             name: The name of the model. Available models are "standard" and "pixelart"
+            grad_mode: which engine differentiates predicted_noise when dtype is "precise" or "mixed": "f16" (default) a second, lazily
+                built f16 engine; "own" the model's own engine (precise only: value and gradient both at that mode's accuracy, no second
+                copy of the weights).  The 16-bit dtypes always use their own engine.
         """
         super().__init__()
+        if grad_mode not in ("f16", "own"):
+            raise ValueError(f"grad_mode must be 'f16' or 'own', got {grad_mode!r}")
+        if grad_mode == "own" and dtype == "mixed":
+            raise NotImplementedError("the mixed mode has no input gradient of its own (engine/adm_mixed.py): use grad_mode='f16' or dtype='precise'")
+        self.grad_mode = grad_mode
         self.name = name
         if config is not None:
             self.config, self.shape = config, (3, config.image_size, config.image_size)
@@ -102,11 +110,11 @@ class GuidedDiffusion(torch.nn.Module):
 
     @property
     def grad_engine(self):
-        """The engine whose training-mode forward + backward give the input gradient: the model's own in the 16-bit modes; a lazily built f16
-        engine for the mixed / precise modes (their split tensors have no backward kernels: the gradient is then the f16 path's, 1.4e-3
-        relative to fp32 autograd on the shipped net, tests/test_gpu_backward.py -- the forward value stays the mode's own)."""
+        """The engine whose training-mode forward + backward give the input gradient: the model's own in the 16-bit modes and in precise mode
+        with grad_mode "own"; otherwise (mixed / precise, grad_mode "f16") a lazily built f16 engine -- the gradient is then the f16 path's,
+        1.4e-3 relative to fp32 autograd on the shipped net, tests/test_gpu_backward.py, while the forward value stays the mode's own."""
         eng = self.engine
-        if eng is None or not getattr(eng, "precise", False):
+        if eng is None or not getattr(eng, "precise", False) or self.grad_mode == "own":
             return eng
         if self.__dict__.get("_grad_engine") is None:
             self.__dict__["_grad_engine"] = adm.AdmEngine(self.config, self.model.state_dict(), self.device, "f16")
