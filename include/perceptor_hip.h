@@ -172,6 +172,21 @@ int pmi_gn_apply_pool_skip(const void* x, const float* coef_a, const float* coef
 int pmi_attn_flash_workspace(int N, int T, int Tk, int heads, int d);
 int pmi_attn_flash(const void* q, int ldq, const void* k, const void* v, int ldkv, void* out, void* ws, int N, int T, int Tk, int heads,
                    int d, float scale, int dtype, pmi_stream_t s);
+/* The same with an input gradient: what autograd forms upstream when a loss on the predicted noise reaches the latents through the
+ * transformer blocks' attention (stable_diffusion/attention.py:268-298 under stable_diffusion.py:259-271).
+ * pmi_attn_flash_train = pmi_attn_flash (same kernels, same output bits) that also writes lse[N*heads][Tp] fp32, Tp = T rounded up to 32,
+ * in the EXP2 domain: lse = log2 sum_s exp2(S[t][s] scale log2 e) (0 for the rows t >= T), and leaves the Q / K fragments in ws.
+ * pmi_attn_flash_bwd recomputes P = exp2(S scale log2 e - lse) per 32 x 32 tile: dP = dO V^T, dS = P o (dP - delta) scale, dQ = dS K,
+ * dK = dS^T Q, dV = P^T dO, delta[t] = sum_c dO[t][c] O[t][c] (written to delta[N*heads][Tp] by its first pass).  out / dout [N][T][heads*d];
+ * ws: the forward's; ws_bwd: pmi_attn_flash_bwd_workspace(...) KiB; dq [N][T][lddq], dk / dv [N][Tk][lddkv], head h at channel offset h*d
+ * (self-attention: three slices of d qkv [N][T][3C]).  dq_only = 1 (cross-attention: k, v come from the frozen prompt encodings,
+ * conditioning.py:16): only dq is written, dk / dv may be NULL.  No atomics: results are run-to-run bit-identical. */
+int pmi_attn_flash_train(const void* q, int ldq, const void* k, const void* v, int ldkv, void* out, void* ws, float* lse, int N, int T, int Tk,
+                         int heads, int d, float scale, int dtype, pmi_stream_t s);
+int pmi_attn_flash_bwd_workspace(int N, int T, int Tk, int heads, int d, int dq_only);
+int pmi_attn_flash_bwd(const void* q, int ldq, const void* k, const void* v, int ldkv, const void* out, const void* dout, const void* ws,
+                       const float* lse, void* ws_bwd, float* delta, void* dq, int lddq, void* dk, void* dv, int lddkv, int N, int T, int Tk,
+                       int heads, int d, float scale, int dq_only, int dtype, pmi_stream_t s);
 int pmi_qkv_split(const void* qkv, void* q, void* k, void* vt, int N, int T, int heads, int order, int dtype, pmi_stream_t s);
 int pmi_attn_d64(const void* q, const void* k, const void* vt, void* out, int N, int T, int heads, float scale,
                  int dtype, pmi_stream_t s);
@@ -199,6 +214,9 @@ int pmi_finish_output(const float* y, int ld, float* out, int N, int H, int W, i
 int pmi_nchw_to_nhwc(const float* in, void* x, int N, int C, int H, int W, int Cpad, float mul, float add, int dtype, pmi_stream_t s);
 int pmi_nhwc_to_nchw(const float* y, int ld, float* out, int N, int H, int W, int cout, float mul, float add, pmi_stream_t s);
 int pmi_geglu(const void* h, void* out, int64_t M, int F, int interleaved, int dtype, pmi_stream_t s);
+/* GEGLU backward (autograd through stable_diffusion/attention.py:346-348): from the kept h[M][2F] and dg[M][F] = d loss / d output,
+ * dh[M][2F] in h's column order: d value = dg gelu(gate), d gate = dg value gelu'(gate) (erf GELU). */
+int pmi_geglu_bwd(const void* h, const void* dg, void* dh, int64_t M, int F, int interleaved, int dtype, pmi_stream_t s);
 int pmi_avgpool2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);            /* nn.AvgPool2d(2) */
 int pmi_upsample_bilinear2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);  /* align_corners=False */
 int pmi_upsample_nearest2(const void* x, void* y, int N, int H, int W, int C, pmi_stream_t s);              /* nn.Upsample(2, 'nearest'), 16-bit NHWC */

@@ -78,6 +78,9 @@ _PROTOS = {
     "pmi_gn_apply": ([_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],),
     "pmi_attn_flash_workspace": ([_I, _I, _I, _I, _I],),
     "pmi_attn_flash": ([_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],),
+    "pmi_attn_flash_train": ([_P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],),
+    "pmi_attn_flash_bwd_workspace": ([_I, _I, _I, _I, _I, _I],),
+    "pmi_attn_flash_bwd": ([_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],),
     "pmi_qkv_split": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],),
     "pmi_attn_d64": ([_P, _P, _P, _P, _I, _I, _I, _F, _I, _P],),
     "pmi_vit_attn_fwd": ([_P, _P, _P, _P, _I, _I, _I, _F, _I, _P],),
@@ -87,6 +90,7 @@ _PROTOS = {
     "pmi_nchw_to_nhwc": ([_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P],),
     "pmi_nhwc_to_nchw": ([_P, _I, _P, _I, _I, _I, _I, _F, _F, _P],),
     "pmi_geglu": ([_P, _P, _L, _I, _I, _I, _P],),
+    "pmi_geglu_bwd": ([_P, _P, _P, _L, _I, _I, _I, _P],),
     "pmi_avgpool2": ([_P, _P, _I, _I, _I, _I, _I, _P],),
     "pmi_upsample_bilinear2": ([_P, _P, _I, _I, _I, _I, _I, _P],),
     "pmi_upsample_nearest2": ([_P, _P, _I, _I, _I, _I, _P],),

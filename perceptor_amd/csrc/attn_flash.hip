@@ -70,7 +70,8 @@ __global__ __launch_bounds__(256) void flash_split_kernel(const u16* __restrict_
 
 template <typename T_, int KQ, int DB, int QT>
 __global__ __launch_bounds__(64) void attn_flash_kernel(const u16* __restrict__ qf, const u16* __restrict__ kf, const u16* __restrict__ vtf,
-                                                        u16* __restrict__ out, int T, int Tk, int heads, int d, float scale_log2e) {
+                                                        u16* __restrict__ out, float* __restrict__ lse, int T, int Tk, int heads, int d,
+                                                        float scale_log2e) {
   const int lane = threadIdx.x, l31 = lane & 31, lhi = lane >> 5;
   const int nx = gridDim.x;
   const int lin = xcd_remap(blockIdx.x + nx * blockIdx.y, nx * gridDim.y);     // all query tiles of a head on one XCD (its K/V stay in that L2)
@@ -161,6 +162,7 @@ __global__ __launch_bounds__(64) void attn_flash_kernel(const u16* __restrict__ 
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
     const int t = (bx * QT + qt) * 32 + l31;
+    if (lse && lhi == 0 && bx * QT + qt < ntq) lse[(int64_t)bh * ntq * 32 + t] = t < T ? m_run[qt] + log2f(l_run[qt]) : 0.f;   // training forward only
     if (t >= T) continue;
     const float inv = 1.f / l_run[qt];
     u16* ob = out + ((int64_t)n * T + t) * (heads * d) + h * d;
@@ -181,7 +183,8 @@ __global__ __launch_bounds__(64) void attn_flash_kernel(const u16* __restrict__ 
 // LDS: one barrier per key block) and the four waves read them from LDS (fragment order: 64 lanes x 16 B contiguous, conflict-free).
 template <typename T_, int KQ, int DB>
 __global__ __launch_bounds__(256) void attn_flash_lds_kernel(const u16* __restrict__ qf, const u16* __restrict__ kf, const u16* __restrict__ vtf,
-                                                            u16* __restrict__ out, int T, int Tk, int heads, int d, float scale_log2e) {
+                                                            u16* __restrict__ out, float* __restrict__ lse, int T, int Tk, int heads, int d,
+                                                            float scale_log2e) {
   constexpr int NP = KQ + 2 * DB;                      // 1 KB fragment pieces per key block
   constexpr int NPI = (NP + 3) / 4;                    // pieces staged per thread
   __shared__ uint4 kv[2][NP * 64];
@@ -273,6 +276,7 @@ __global__ __launch_bounds__(256) void attn_flash_lds_kernel(const u16* __restri
     __syncthreads();
   }
   const int t = tq * 32 + l31;
+  if (lse && lhi == 0 && tq < ntq) lse[(int64_t)bh * ntq * 32 + t] = t < T ? m_run + log2f(l_run) : 0.f;       // training forward only
   if (tq >= ntq || t >= T) return;
   const int n = bh / heads, h = bh - n * heads;
   const float inv = 1.f / l_run;
@@ -291,29 +295,273 @@ __global__ __launch_bounds__(256) void attn_flash_lds_kernel(const u16* __restri
 static int g_flash_qt = 0;       // A/B switch (pmi_set_option 9): 0 = automatic (LDS-shared kernel for long sequences), 1 / 2 = one-wave kernel with 1 / 2 query tiles per wave
 
 template <typename T_, int KQ, int DB>
-void launch_flash(const u16* qf, const u16* kf, const u16* vtf, u16* out, int N, int T, int Tk, int heads, int d, float sl2, hipStream_t st) {
+void launch_flash(const u16* qf, const u16* kf, const u16* vtf, u16* out, float* lse, int N, int T, int Tk, int heads, int d, float sl2, hipStream_t st) {
   const int ntq = (T + 31) / 32;
   // two query tiles per wave where the sequence is long enough to still fill the chip (and the accumulators fit: DB <= 3)
   if (g_flash_qt != 1 && g_flash_qt != 2 && ntq >= 64) {     // long query sequences (T >= 2048): four waves per workgroup share K / V^T through LDS (0.61 vs 0.65 ms at T = 4096)
-    hipLaunchKernelGGL((attn_flash_lds_kernel<T_, KQ, DB>), dim3((ntq + 3) / 4, N * heads), dim3(256), 0, st, qf, kf, vtf, out, T, Tk, heads, d, sl2);
+    hipLaunchKernelGGL((attn_flash_lds_kernel<T_, KQ, DB>), dim3((ntq + 3) / 4, N * heads), dim3(256), 0, st, qf, kf, vtf, out, lse, T, Tk, heads, d, sl2);
     return;
   }
   if constexpr (DB <= 2) {
     if (g_flash_qt == 2) {      // measured at T = 4096, d = 40: 0.85 ms against 0.65 ms with one tile per wave (204 VGPRs: one wave per SIMD)
-      hipLaunchKernelGGL((attn_flash_kernel<T_, KQ, DB, 2>), dim3((ntq + 1) / 2, N * heads), dim3(64), 0, st, qf, kf, vtf, out, T, Tk, heads, d, sl2);
+      hipLaunchKernelGGL((attn_flash_kernel<T_, KQ, DB, 2>), dim3((ntq + 1) / 2, N * heads), dim3(64), 0, st, qf, kf, vtf, out, lse, T, Tk, heads, d, sl2);
       return;
     }
   }
-  hipLaunchKernelGGL((attn_flash_kernel<T_, KQ, DB, 1>), dim3(ntq, N * heads), dim3(64), 0, st, qf, kf, vtf, out, T, Tk, heads, d, sl2);
+  hipLaunchKernelGGL((attn_flash_kernel<T_, KQ, DB, 1>), dim3(ntq, N * heads), dim3(64), 0, st, qf, kf, vtf, out, lse, T, Tk, heads, d, sl2);
 }
 
 template <typename T_>
-int dispatch_flash(const u16* qf, const u16* kf, const u16* vtf, u16* out, int N, int T, int Tk, int heads, int d, float sl2, hipStream_t st) {
+int dispatch_flash(const u16* qf, const u16* kf, const u16* vtf, u16* out, float* lse, int N, int T, int Tk, int heads, int d, float sl2, hipStream_t st) {
   const int KQ = (d + 15) / 16, DB = (d + 31) / 32;
-#define CASE(kq, db) if (KQ == kq && DB == db) { launch_flash<T_, kq, db>(qf, kf, vtf, out, N, T, Tk, heads, d, sl2, st); return PMI_OK; }
+#define CASE(kq, db) if (KQ == kq && DB == db) { launch_flash<T_, kq, db>(qf, kf, vtf, out, lse, N, T, Tk, heads, d, sl2, st); return PMI_OK; }
   CASE(1, 1) CASE(2, 1) CASE(3, 2) CASE(4, 2) CASE(5, 3) CASE(6, 3) CASE(7, 4) CASE(8, 4) CASE(9, 5) CASE(10, 5)
 #undef CASE
   return PMI_ERR_ARG;
+}
+
+
+// ---- backward: P recomputed per 32 x 32 tile from the forward's log-sum-exp, no T x Tk matrix in HBM, no atomics ---------------------------
+// The scheme of attn.hip's 64-channel vit_attn_bwd_kernel, generalised to KQ k-steps / DB channel blocks and a separate key length:
+//   dQ role   : one wave per 32-query tile, loops over key tiles.   S^T = K Q^T and dP^T = V dO^T put the query on the lane (lse, delta are
+//               lane-local); dS^T, still in the accumulator, is the B operand of dQ^T += K^T dS^T.
+//   dK/dV role: one wave per 32-key tile, loops over query tiles.   S = Q K^T and dP = dO V^T put the key on the lane; P and dS are the B
+//               operands of dV^T += dO^T P and dK^T += Q^T dS.
+// Both roles of a layer are one launch (workgroups [0, ntk) own key tiles, the rest query tiles); cross-attention compiles the dQ role
+// alone.  Every output element is written once by one wave in a fixed order: run-to-run bit-identical.
+// Extra fragments (flash_bwd_split_kernel): dO and V in Q / K order, K^T (and, with dK / dV, dO^T and Q^T) in V^T order;
+// delta[bh][t] = sum_c dO[t][c] O[t][c] fp32.  P = exp2(S scale log2e - lse): lse is in the exp2 domain, as the forward's running maximum.
+template <typename T_>
+__global__ __launch_bounds__(256) void flash_bwd_split_kernel(const u16* __restrict__ q, int ldq, const u16* __restrict__ k, const u16* __restrict__ v,
+                                                              int ldkv, const u16* __restrict__ o, const u16* __restrict__ dout,
+                                                              u16* __restrict__ dof, u16* __restrict__ vf, u16* __restrict__ ktf,
+                                                              u16* __restrict__ dotf, u16* __restrict__ qtf, float* __restrict__ delta, int T, int Tk,
+                                                              int heads, int d, int KQ, int DB, int dq_only) {
+  __shared__ u16 sv[32][168];
+  const int tb = blockIdx.x, bh = blockIdx.y, n = bh / heads, h = bh - n * heads;
+  const int ntq = (T + 31) >> 5, ntk = (Tk + 31) >> 5, C = heads * d;
+  if (tb < ntq) {
+    split_block<false>(dout, C, dof, n, h, bh, tb, T, ntq, d, KQ, DB, sv);
+    const int tid = threadIdx.x, row = tid >> 3, ch = tid & 7, t = tb * 32 + row;
+    float p = 0.f;
+    if (t < T) {
+      const int64_t off = ((int64_t)n * T + t) * C + h * d;
+      for (int c8 = ch; c8 * 8 < d; c8 += 8) {
+        float a[8], b[8];
+        unpack8<T_>(*(const uint4*)(dout + off + c8 * 8), a);
+        unpack8<T_>(*(const uint4*)(o + off + c8 * 8), b);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) p += a[e] * b[e];
+      }
+    }
+    p += __shfl_xor(p, 1); p += __shfl_xor(p, 2); p += __shfl_xor(p, 4);
+    if (ch == 0) delta[(int64_t)bh * ntq * 32 + t] = p;
+    if (!dq_only) {
+      split_block<true>(dout, C, dotf, n, h, bh, tb, T, ntq, d, KQ, DB, sv);
+      split_block<true>(q, ldq, qtf, n, h, bh, tb, T, ntq, d, KQ, DB, sv);
+    }
+  }
+  if (tb < ntk) {
+    split_block<false>(v, ldkv, vf, n, h, bh, tb, Tk, ntk, d, KQ, DB, sv);
+    split_block<true>(k, ldkv, ktf, n, h, bh, tb, Tk, ntk, d, KQ, DB, sv);
+  }
+}
+
+// channel rows of an accumulator block set (the forward's output order) -> rows of dst [..][ld], head channels [0, d)
+template <typename T_, int DB>
+__device__ __forceinline__ void store_rows(const f32x16* acc, u16* dst, int d, int lhi) {
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int c = 32 * db + 8 * g + 4 * lhi;
+      if (c < d) *(uint2*)(dst + c) = pack4<T_>(acc[db][4 * g], acc[db][4 * g + 1], acc[db][4 * g + 2], acc[db][4 * g + 3]);
+    }
+}
+
+template <typename T_, int KQ, int DB>
+__device__ __forceinline__ void flash_dq_body(const u16* __restrict__ qf, const u16* __restrict__ dof, const u16* __restrict__ kf,
+                                              const u16* __restrict__ vf, const u16* __restrict__ ktf, const float* __restrict__ lse,
+                                              const float* __restrict__ delta, u16* __restrict__ dq, int lddq, int T, int Tk, int heads, int d,
+                                              float sl2, float scale, int bx, int bh) {
+  const int lane = threadIdx.x, l31 = lane & 31, lhi = lane >> 5;
+  const int ntq = (T + 31) >> 5, ntk = (Tk + 31) >> 5;
+  uint4 qr[KQ], dor[KQ];
+#pragma unroll
+  for (int kk = 0; kk < KQ; ++kk) {
+    qr[kk] = *(const uint4*)(qf + rfrag_g((int64_t)bh * ntq + bx, KQ, kk, lhi, l31));
+    dor[kk] = *(const uint4*)(dof + rfrag_g((int64_t)bh * ntq + bx, KQ, kk, lhi, l31));
+  }
+  const float nlse = -lse[((int64_t)bh * ntq + bx) * 32 + l31], my_delta = delta[((int64_t)bh * ntq + bx) * 32 + l31];
+  f32x16 g[DB];
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) g[db][r] = 0.f;
+  for (int sb = 0; sb < ntk; ++sb) {
+    const int64_t blk = (int64_t)bh * ntk + sb;
+    f32x16 sacc, dp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+    for (int kk = 0; kk < KQ; ++kk) {
+      sacc = T_::mfma32(*(const uint4*)(kf + rfrag_g(blk, KQ, kk, lhi, l31)), qr[kk], sacc);
+      dp = T_::mfma32(*(const uint4*)(vf + rfrag_g(blk, KQ, kk, lhi, l31)), dor[kk], dp);
+    }
+    const bool tail = (sb + 1) * 32 > Tk;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float p = exp2f(fmaf(sacc[r], sl2, nlse));
+      if (tail && sb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi >= Tk) p = 0.f;       // a padded key has no weight
+      sacc[r] = p * (dp[r] - my_delta) * scale;                                    // dS^T[s][t]
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      float f[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = sacc[8 * ks + j];
+      const uint4 dsf = pack8<T_>(f);
+#pragma unroll
+      for (int db = 0; db < DB; ++db) g[db] = T_::mfma32(*(const uint4*)(ktf + tfrag_g(blk, DB, ks, db, lhi, l31)), dsf, g[db]);
+    }
+  }
+  const int t = bx * 32 + l31;
+  if (t >= T) return;
+  const int n = bh / heads, h = bh - n * heads;
+  store_rows<T_, DB>(g, dq + ((int64_t)n * T + t) * lddq + h * d, d, lhi);
+}
+
+template <typename T_, int KQ, int DB>
+__device__ __forceinline__ void flash_dkdv_body(const u16* __restrict__ qf, const u16* __restrict__ dof, const u16* __restrict__ kf,
+                                                const u16* __restrict__ vf, const u16* __restrict__ qtf, const u16* __restrict__ dotf,
+                                                const float* __restrict__ lse, const float* __restrict__ delta, u16* __restrict__ dk,
+                                                u16* __restrict__ dv, int lddkv, int T, int Tk, int heads, int d, float sl2, float scale, int bx,
+                                                int bh) {
+  const int lane = threadIdx.x, l31 = lane & 31, lhi = lane >> 5;
+  const int ntq = (T + 31) >> 5, ntk = (Tk + 31) >> 5;
+  uint4 kr[KQ], vr[KQ];
+#pragma unroll
+  for (int kk = 0; kk < KQ; ++kk) {
+    kr[kk] = *(const uint4*)(kf + rfrag_g((int64_t)bh * ntk + bx, KQ, kk, lhi, l31));
+    vr[kk] = *(const uint4*)(vf + rfrag_g((int64_t)bh * ntk + bx, KQ, kk, lhi, l31));
+  }
+  const bool key_ok = bx * 32 + l31 < Tk;
+  f32x16 gk[DB], gv[DB];
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { gk[db][r] = 0.f; gv[db][r] = 0.f; }
+  for (int tb = 0; tb < ntq; ++tb) {
+    const int64_t blk = (int64_t)bh * ntq + tb;
+    // the 16 query rows of this lane's accumulator registers: 4 runs of 4 consecutive rows
+    float4 ls[4], dl[4];
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+      ls[g4] = *(const float4*)(lse + blk * 32 + 8 * g4 + 4 * lhi);
+      dl[g4] = *(const float4*)(delta + blk * 32 + 8 * g4 + 4 * lhi);
+    }
+    f32x16 sacc, dp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+    for (int kk = 0; kk < KQ; ++kk) {
+      sacc = T_::mfma32(*(const uint4*)(qf + rfrag_g(blk, KQ, kk, lhi, l31)), kr[kk], sacc);        // rows = queries, lane = key
+      dp = T_::mfma32(*(const uint4*)(dof + rfrag_g(blk, KQ, kk, lhi, l31)), vr[kk], dp);
+    }
+    const bool tail = (tb + 1) * 32 > T;
+    float pf[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float* l4 = (const float*)&ls[r >> 2];
+      const float* d4 = (const float*)&dl[r >> 2];
+      float p = key_ok ? exp2f(fmaf(sacc[r], sl2, -l4[r & 3])) : 0.f;
+      if (tail && tb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi >= T) p = 0.f;
+      pf[r] = p;
+      sacc[r] = p * (dp[r] - d4[r & 3]) * scale;                                                     // dS[t][s]
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const uint4 pfrag = pack8<T_>(pf + 8 * ks);
+      float f[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = sacc[8 * ks + j];
+      const uint4 dsf = pack8<T_>(f);
+#pragma unroll
+      for (int db = 0; db < DB; ++db) {
+        gv[db] = T_::mfma32(*(const uint4*)(dotf + tfrag_g(blk, DB, ks, db, lhi, l31)), pfrag, gv[db]);
+        gk[db] = T_::mfma32(*(const uint4*)(qtf + tfrag_g(blk, DB, ks, db, lhi, l31)), dsf, gk[db]);
+      }
+    }
+  }
+  const int s = bx * 32 + l31;
+  if (s >= Tk) return;
+  const int n = bh / heads, h = bh - n * heads;
+  const int64_t off = ((int64_t)n * Tk + s) * lddkv + h * d;
+  store_rows<T_, DB>(gk, dk + off, d, lhi);
+  store_rows<T_, DB>(gv, dv + off, d, lhi);
+}
+
+struct FlashBwdArgs {
+  const u16 *qf, *kf, *dof, *vf, *ktf, *dotf, *qtf;
+  const float *lse, *delta;
+  u16 *dq, *dk, *dv;
+  int lddq, lddkv, T, Tk, heads, d;
+  float sl2, scale;
+};
+
+template <typename T_, int KQ, int DB, bool DQ_ONLY>
+__global__ __launch_bounds__(64) void attn_flash_bwd_kernel(const FlashBwdArgs a) {
+  const int nx = gridDim.x;
+  const int lin = xcd_remap(blockIdx.x + nx * blockIdx.y, nx * gridDim.y);     // a head's tiles on one XCD, as the forward
+  const int bh = lin / nx, bx = lin - bh * nx;
+  const int ntk = (a.Tk + 31) >> 5;
+  if constexpr (DQ_ONLY) {
+    flash_dq_body<T_, KQ, DB>(a.qf, a.dof, a.kf, a.vf, a.ktf, a.lse, a.delta, a.dq, a.lddq, a.T, a.Tk, a.heads, a.d, a.sl2, a.scale, bx, bh);
+  } else {
+    if (bx < ntk)      // the key-tile role first: it carries two accumulator sets and the longer loop body
+      flash_dkdv_body<T_, KQ, DB>(a.qf, a.dof, a.kf, a.vf, a.qtf, a.dotf, a.lse, a.delta, a.dk, a.dv, a.lddkv, a.T, a.Tk, a.heads, a.d, a.sl2,
+                                  a.scale, bx, bh);
+    else
+      flash_dq_body<T_, KQ, DB>(a.qf, a.dof, a.kf, a.vf, a.ktf, a.lse, a.delta, a.dq, a.lddq, a.T, a.Tk, a.heads, a.d, a.sl2, a.scale, bx - ntk,
+                                bh);
+  }
+}
+
+template <typename T_>
+int dispatch_flash_bwd(const FlashBwdArgs& a, int N, bool dq_only, hipStream_t st) {
+  const int KQ = (a.d + 15) / 16, DB = (a.d + 31) / 32, ntq = (a.T + 31) / 32, ntk = (a.Tk + 31) / 32;
+  const dim3 grid(dq_only ? ntq : ntq + ntk, N * a.heads);
+#define CASE(kq, db)                                                                                          \
+  if (KQ == kq && DB == db) {                                                                                 \
+    if (dq_only) hipLaunchKernelGGL((attn_flash_bwd_kernel<T_, kq, db, true>), grid, dim3(64), 0, st, a);     \
+    else hipLaunchKernelGGL((attn_flash_bwd_kernel<T_, kq, db, false>), grid, dim3(64), 0, st, a);            \
+    return PMI_OK;                                                                                            \
+  }
+  CASE(1, 1) CASE(2, 1) CASE(3, 2) CASE(4, 2) CASE(5, 3) CASE(6, 3) CASE(7, 4) CASE(8, 4) CASE(9, 5) CASE(10, 5)
+#undef CASE
+  return PMI_ERR_ARG;
+}
+
+bool flash_args_ok(const void* q, int ldq, const void* k, const void* v, int ldkv, int N, int T, int Tk, int heads, int d, int dtype) {
+  return q && k && v && N > 0 && T > 0 && Tk > 0 && heads > 0 && d > 0 && d <= 160 && !(d & 7) && ldq >= heads * d && ldkv >= heads * d &&
+         !(ldq & 7) && !(ldkv & 7) && (dtype == PMI_DT_BF16 || dtype == PMI_DT_F16);
+}
+
+int flash_forward(const void* q, int ldq, const void* k, const void* v, int ldkv, void* out, void* ws, float* lse, int N, int T, int Tk, int heads,
+                  int d, float scale, int dtype, hipStream_t st) {
+  const int64_t KQ = (d + 15) / 16, DB = (d + 31) / 32, ntq = (T + 31) / 32, ntk = (Tk + 31) / 32;
+  u16* qf = (u16*)ws;
+  u16* kf = qf + (int64_t)N * heads * ntq * KQ * 512;
+  u16* vtf = kf + (int64_t)N * heads * ntk * KQ * 512;
+  hipLaunchKernelGGL(flash_split_kernel, dim3((unsigned)(ntq > ntk ? ntq : ntk), N * heads), dim3(256), 0, st, (const u16*)q, ldq, (const u16*)k,
+                     (const u16*)v, ldkv, qf, kf, vtf, T, Tk, heads, d, (int)KQ, (int)DB);
+  PMI_CHECK_LAUNCH();
+  const float sl2 = scale * 1.4426950408889634f;
+  const int rc = dtype == PMI_DT_BF16 ? dispatch_flash<BF16>(qf, kf, vtf, (u16*)out, lse, N, T, Tk, heads, d, sl2, st)
+                                      : dispatch_flash<F16>(qf, kf, vtf, (u16*)out, lse, N, T, Tk, heads, d, sl2, st);
+  if (rc != PMI_OK) return rc;
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
 }
 
 }  // namespace
@@ -329,20 +577,55 @@ extern "C" int pmi_attn_flash_workspace(int N, int T, int Tk, int heads, int d) 
 
 extern "C" int pmi_attn_flash(const void* q, int ldq, const void* k, const void* v, int ldkv, void* out, void* ws, int N, int T, int Tk,
                               int heads, int d, float scale, int dtype, pmi_stream_t s) {
-  if (!q || !k || !v || !out || !ws || N <= 0 || T <= 0 || Tk <= 0 || heads <= 0 || d <= 0 || d > 160 || (d & 7) || ldq < heads * d ||
-      ldkv < heads * d || (ldq & 7) || (ldkv & 7) || (dtype != PMI_DT_BF16 && dtype != PMI_DT_F16))
-    return PMI_ERR_ARG;
+  if (!flash_args_ok(q, ldq, k, v, ldkv, N, T, Tk, heads, d, dtype) || !out || !ws) return PMI_ERR_ARG;
+  return flash_forward(q, ldq, k, v, ldkv, out, ws, nullptr, N, T, Tk, heads, d, scale, dtype, (hipStream_t)s);
+}
+
+extern "C" int pmi_attn_flash_train(const void* q, int ldq, const void* k, const void* v, int ldkv, void* out, void* ws, float* lse, int N, int T,
+                                    int Tk, int heads, int d, float scale, int dtype, pmi_stream_t s) {
+  if (!flash_args_ok(q, ldq, k, v, ldkv, N, T, Tk, heads, d, dtype) || !out || !ws || !lse) return PMI_ERR_ARG;
+  return flash_forward(q, ldq, k, v, ldkv, out, ws, lse, N, T, Tk, heads, d, scale, dtype, (hipStream_t)s);
+}
+
+extern "C" int pmi_attn_flash_bwd_workspace(int N, int T, int Tk, int heads, int d, int dq_only) {       // in KiB
+  if (N <= 0 || T <= 0 || Tk <= 0 || heads <= 0 || d <= 0 || d > 160 || (d & 7)) return -1;
   const int64_t KQ = (d + 15) / 16, DB = (d + 31) / 32, ntq = (T + 31) / 32, ntk = (Tk + 31) / 32;
-  u16* qf = (u16*)ws;
-  u16* kf = qf + (int64_t)N * heads * ntq * KQ * 512;
-  u16* vtf = kf + (int64_t)N * heads * ntk * KQ * 512;
+  const int64_t kib = (int64_t)N * heads * (ntq * KQ + ntk * KQ + ntk * DB * 2 + (dq_only ? 0 : ntq * DB * 4));
+  return kib > 0x7fffffff ? -1 : (int)kib;
+}
+
+extern "C" int pmi_attn_flash_bwd(const void* q, int ldq, const void* k, const void* v, int ldkv, const void* out, const void* dout,
+                                  const void* ws, const float* lse, void* ws_bwd, float* delta, void* dq, int lddq, void* dk, void* dv, int lddkv,
+                                  int N, int T, int Tk, int heads, int d, float scale, int dq_only, int dtype, pmi_stream_t s) {
+  if (!flash_args_ok(q, ldq, k, v, ldkv, N, T, Tk, heads, d, dtype) || !out || !dout || !ws || !lse || !ws_bwd || !delta || !dq ||
+      lddq < heads * d || (lddq & 3))
+    return PMI_ERR_ARG;
+  if (!dq_only && (!dk || !dv || lddkv < heads * d || (lddkv & 3))) return PMI_ERR_ARG;
+  const int64_t KQ = (d + 15) / 16, DB = (d + 31) / 32, ntq = (T + 31) / 32, ntk = (Tk + 31) / 32, NH = (int64_t)N * heads;
+  FlashBwdArgs a;
+  a.qf = (const u16*)ws;
+  a.kf = a.qf + NH * ntq * KQ * 512;
+  u16* dof = (u16*)ws_bwd;
+  u16* vf = dof + NH * ntq * KQ * 512;
+  u16* ktf = vf + NH * ntk * KQ * 512;
+  u16* dotf = ktf + NH * ntk * DB * 1024;
+  u16* qtf = dotf + NH * ntq * DB * 1024;
+  if (dq_only) dotf = qtf = nullptr;
   hipStream_t st = (hipStream_t)s;
-  hipLaunchKernelGGL(flash_split_kernel, dim3((unsigned)(ntq > ntk ? ntq : ntk), N * heads), dim3(256), 0, st, (const u16*)q, ldq, (const u16*)k,
-                     (const u16*)v, ldkv, qf, kf, vtf, T, Tk, heads, d, (int)KQ, (int)DB);
+  const dim3 sg((unsigned)(ntq > ntk ? ntq : ntk), (unsigned)NH);
+  if (dtype == PMI_DT_BF16)
+    hipLaunchKernelGGL(flash_bwd_split_kernel<BF16>, sg, dim3(256), 0, st, (const u16*)q, ldq, (const u16*)k, (const u16*)v, ldkv, (const u16*)out,
+                       (const u16*)dout, dof, vf, ktf, dotf, qtf, delta, T, Tk, heads, d, (int)KQ, (int)DB, dq_only);
+  else
+    hipLaunchKernelGGL(flash_bwd_split_kernel<F16>, sg, dim3(256), 0, st, (const u16*)q, ldq, (const u16*)k, (const u16*)v, ldkv, (const u16*)out,
+                       (const u16*)dout, dof, vf, ktf, dotf, qtf, delta, T, Tk, heads, d, (int)KQ, (int)DB, dq_only);
   PMI_CHECK_LAUNCH();
-  const float sl2 = scale * 1.4426950408889634f;
-  const int rc = dtype == PMI_DT_BF16 ? dispatch_flash<BF16>(qf, kf, vtf, (u16*)out, N, T, Tk, heads, d, sl2, st)
-                                      : dispatch_flash<F16>(qf, kf, vtf, (u16*)out, N, T, Tk, heads, d, sl2, st);
+  a.dof = dof; a.vf = vf; a.ktf = ktf; a.dotf = dotf; a.qtf = qtf;
+  a.lse = lse; a.delta = delta;
+  a.dq = (u16*)dq; a.dk = (u16*)dk; a.dv = (u16*)dv;
+  a.lddq = lddq; a.lddkv = lddkv; a.T = T; a.Tk = Tk; a.heads = heads; a.d = d;
+  a.scale = scale; a.sl2 = scale * 1.4426950408889634f;
+  const int rc = dtype == PMI_DT_BF16 ? dispatch_flash_bwd<BF16>(a, N, dq_only != 0, st) : dispatch_flash_bwd<F16>(a, N, dq_only != 0, st);
   if (rc != PMI_OK) return rc;
   PMI_CHECK_LAUNCH();
   return PMI_OK;

@@ -97,6 +97,32 @@ __global__ __launch_bounds__(256) void geglu_kernel(const u16* __restrict__ h, u
   }
 }
 
+// GEGLU backward from the kept pre-activation h[M][2F] and dg = d loss / d (value * gelu(gate)) [M][F]: d value = dg gelu(gate),
+// d gate = dg value gelu'(gate), written in h's own column order (the ff1 dX GEMM reads it as it is)
+template <typename T>
+__global__ __launch_bounds__(256) void geglu_bwd_kernel(const u16* __restrict__ h, const u16* __restrict__ dg, u16* __restrict__ dh, int64_t M, int F,
+                                                        int interleaved) {
+  const int F8 = F >> 3;
+  const int64_t total = M * F8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c8 = (int)(i % F8);
+    const int64_t r = i / F8;
+    float v[8], g[8], d[8];
+    const int vo = interleaved ? (c8 >> 1) * 32 + (c8 & 1) * 8 : c8 * 8, go = interleaved ? vo + 16 : F + c8 * 8;
+    unpack8<T>(*(const uint4*)(h + r * 2 * F + vo), v);
+    unpack8<T>(*(const uint4*)(h + r * 2 * F + go), g);
+    unpack8<T>(*(const uint4*)(dg + r * F + c8 * 8), d);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float gel = 0.5f * g[e] * (1.f + fast_erff(g[e] * 0.70710678118654752f));
+      g[e] = d[e] * v[e] * act_grad(g[e], PMI_ACT_GELU);
+      v[e] = d[e] * gel;
+    }
+    *(uint4*)(dh + r * 2 * F + vo) = pack8<T>(v);
+    *(uint4*)(dh + r * 2 * F + go) = pack8<T>(g);
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void avgpool2_kernel(const u16* __restrict__ x, u16* __restrict__ y, int N, int H, int W, int C) {
   const int C8 = C >> 3, Ho = H / 2, Wo = W / 2;
@@ -338,6 +364,14 @@ extern "C" int pmi_geglu(const void* h, void* out, int64_t M, int F, int interle
   dim3 grid(grid_for(M * (F / 8))), block(256);
   if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(geglu_kernel<BF16>, grid, block, 0, ST, (const u16*)h, (u16*)out, M, F, interleaved);
   else hipLaunchKernelGGL(geglu_kernel<F16>, grid, block, 0, ST, (const u16*)h, (u16*)out, M, F, interleaved);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+extern "C" int pmi_geglu_bwd(const void* h, const void* dg, void* dh, int64_t M, int F, int interleaved, int dtype, pmi_stream_t s) {
+  if (!h || !dg || !dh || M <= 0 || F <= 0 || (F & 7) || (interleaved && (F & 15)) || dtype == PMI_DT_F16X2) return PMI_ERR_ARG;
+  dim3 grid(grid_for(M * (F / 8))), block(256);
+  if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(geglu_bwd_kernel<BF16>, grid, block, 0, ST, (const u16*)h, (const u16*)dg, (u16*)dh, M, F, interleaved);
+  else hipLaunchKernelGGL(geglu_bwd_kernel<F16>, grid, block, 0, ST, (const u16*)h, (const u16*)dg, (u16*)dh, M, F, interleaved);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }

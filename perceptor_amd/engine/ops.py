@@ -793,6 +793,94 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
     return out
 
 
+def flash_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, d: int, dt: int):
+    """flash_attention keeping what flash_attention_backward needs: (out, saved).  Same kernels and output bits as flash_attention; kept are
+    the operand views, the forward's fragment workspace, the output and lse [N*heads, Tp] fp32 (exp2 domain) -- no probabilities."""
+    n, t = q.shape[:2]
+    tk = k.shape[1]
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and k.stride(1) == v.stride(1)
+    assert q.stride(0) == t * q.stride(1) and k.stride(0) == tk * k.stride(1)
+    kib = _hip.lib().pmi_attn_flash_workspace(n, t, tk, heads, d)
+    if kib < 0:
+        raise ValueError(f"flash attention: unsupported head dim {d}")
+    ws = _empty((kib * 512,), q.dtype, q.device)
+    lse = _empty((n * heads, (t + 31) // 32 * 32), torch.float32, q.device)
+    out = _empty((n, t, heads * d), q.dtype, q.device)
+    call("pmi_attn_flash_train", ptr(q), q.stride(1), ptr(k), ptr(v), k.stride(1), ptr(out), ptr(ws), ptr(lse), n, t, tk, heads, d,
+         float(d) ** -0.5, dt)
+    return out, (q, k, v, ws, lse, out)
+
+
+def flash_attention_backward(saved, d_out: torch.Tensor, heads: int, d: int, dt: int, dq_only: bool = False) -> torch.Tensor:
+    """Gradient of flash_attention_train from d loss / d out [N, T, heads*d] (pmi_attn_flash_bwd: P recomputed per tile from lse).
+    Self-attention (q, k, v are the three slices of one qkv tensor): d qkv [N, T, 3C], channels (q|k|v, head, d).  dq_only (cross-attention,
+    constant k / v): dq [N, T, C] alone."""
+    q, k, v, ws, lse, out = saved
+    n, t = q.shape[:2]
+    tk, c = k.shape[1], heads * d
+    assert d_out.is_contiguous() and tuple(d_out.shape) == (n, t, c)
+    kib = _hip.lib().pmi_attn_flash_bwd_workspace(n, t, tk, heads, d, int(dq_only))
+    wsb = _empty((kib * 512,), q.dtype, q.device)
+    delta = torch.empty_like(lse)
+    if dq_only:
+        g = _empty((n, t, c), q.dtype, q.device)
+        dk = dv = None
+        lddkv = 0
+    else:
+        assert tk == t
+        g = _empty((n, t, 3 * c), q.dtype, q.device)
+        dk, dv, lddkv = g[..., c:], g[..., 2 * c:], 3 * c
+    call("pmi_attn_flash_bwd", ptr(q), q.stride(1), ptr(k), ptr(v), k.stride(1), ptr(out), ptr(d_out), ptr(ws), ptr(lse), ptr(wsb), ptr(delta),
+         ptr(g), g.stride(1), ptr(dk), ptr(dv), lddkv, n, t, tk, heads, d, float(d) ** -0.5, int(dq_only), dt)
+    return g
+
+
+def cross_attention_train(q: torch.Tensor, kv: torch.Tensor, heads: int, dt: int):
+    """cross_attention's batched-GEMM route keeping the softmax: (out [N, T, C], P [N*heads, T, Tcp] 16-bit)."""
+    n, t, c = q.shape
+    tc = kv.shape[1]
+    d = c // heads
+    tcp = (tc + 7) // 8 * 8
+    dev = q.device
+    s = _empty((n * heads, t, tcp), torch.float32, dev)
+    bgemm(q, kv, s, M=t, N=tc, K=d, lda=c, ldb=2 * c, ldd=tcp, batch=n * heads, batch_inner=heads,
+          sA=(t * c, d), sB=(tc * 2 * c, d), sD=(heads * t * tcp, t * tcp), dt=dt)
+    p = _empty((n * heads, t, tcp), q.dtype, dev)
+    call("pmi_softmax_fwd", ptr(s), ptr(p), n * heads * t, tc, tcp, tcp, float(d) ** -0.5, dt)
+    vt = _transpose16(kv, c, tc, d, 2 * c, tc * 2 * c, d, heads, n * heads)
+    out = _empty((n, t, c), q.dtype, dev)
+    bgemm(p, vt, out, M=t, N=d, K=tcp, lda=tcp, ldb=tcp, ldd=c, batch=n * heads, batch_inner=heads,
+          sA=(heads * t * tcp, t * tcp), sB=(heads * d * tcp, d * tcp), sD=(t * c, d), dt=dt)
+    return out, p
+
+
+def cross_attention_backward(kv: torch.Tensor, p: torch.Tensor, d_out: torch.Tensor, heads: int, dt: int) -> torch.Tensor:
+    """d loss / d q [N, T, C] of cross_attention_train from the kept softmax (k and v are constants of the backward): dP = dO V^T,
+    dS = softmax'(P, dP), dQ = dS K."""
+    n, t, c = d_out.shape
+    tc = kv.shape[1]
+    d = c // heads
+    tcp = (tc + 7) // 8 * 8
+    dev = d_out.device
+    dp = _empty((n * heads, t, tcp), torch.float32, dev)
+    bgemm(d_out, kv, dp, M=t, N=tc, K=d, lda=c, ldb=2 * c, ldd=tcp, batch=n * heads, batch_inner=heads,
+          sA=(t * c, d), sB=(tc * 2 * c, d), sD=(heads * t * tcp, t * tcp), dt=dt, b_off=c)
+    ds = _empty((n * heads, t, tcp), d_out.dtype, dev)
+    call("pmi_softmax_bwd", ptr(dp), ptr(p), ptr(ds), n * heads * t, tc, tcp, tcp, float(d) ** -0.5, dt)
+    kt = _transpose16(kv, 0, tc, d, 2 * c, tc * 2 * c, d, heads, n * heads)
+    dq = _empty((n, t, c), d_out.dtype, dev)
+    bgemm(ds, kt, dq, M=t, N=d, K=tcp, lda=tcp, ldb=tcp, ldd=c, batch=n * heads, batch_inner=heads,
+          sA=(heads * t * tcp, t * tcp), sB=(heads * d * tcp, d * tcp), sD=(t * c, d), dt=dt)
+    return dq
+
+
+def geglu_backward(h: torch.Tensor, dg: torch.Tensor, dt: int) -> torch.Tensor:
+    """d loss / d h [M, 2F] from the kept pre-activation h (16 value | 16 gate column groups) and dg = d loss / d (value * gelu(gate)) [M, F]."""
+    dh = torch.empty_like(h)
+    call("pmi_geglu_bwd", ptr(h), ptr(dg), ptr(dh), h.shape[0], dg.shape[1], 1, dt)
+    return dh
+
+
 def cross_attention(q: torch.Tensor, kv: torch.Tensor, heads: int, dt: int) -> torch.Tensor:
     """softmax(q k^T d^-1/2) v with keys / values from another sequence (stable_diffusion/attention.py:268-298, the fused call at :285).
     q [N, T, C], kv [N, Tc, 2C] = (k | v) x (head, d), 16-bit -> [N, T, C].  Batched MFMA GEMMs + fp32 softmax (Tc = 77 prompt tokens)."""

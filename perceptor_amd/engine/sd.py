@@ -285,6 +285,12 @@ class _Blocks:
         assert (k + ".skip") in w or x1 is None
         return ops.igemm(h, w[k + ".conv2"], residual=skip, prologue=(ca, cb, ACT_SILU), want_stats=True)
 
+    def _up_back(self, k, g, sd):
+        """Gradient wrt the input of nearest-x2 + conv3x3 from g = gradient wrt its output [N, 2h, 2w, C]: one stride-2 pass on the
+        phase-folded weights, faster at all three SD-v1 shapes than dX at the high resolution + the 2x2 sum (DESIGN.md §11)."""
+        if k + ".fold" not in self.w:
+            self.w[k + ".fold"] = PackedLinear(fold_upsample_weights(sd[k + ".weight"].cpu()).float(), None, self.dt, self.device)
+        return ops.igemm(g, self.w[k + ".fold"], stride=2)
 
     def _pack_vae_attention(self, a):
         sd = self.sd
@@ -397,9 +403,8 @@ class SdUnetEngine(_Blocks):
             h1 = None
         return h
 
-    @torch.no_grad()
-    def forward(self, latents: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor) -> torch.Tensor:
-        """latents NCHW fp32 [N, in, h, w], timesteps [N], context [N, T, context_dim] fp32 -> predicted noise NCHW fp32."""
+    def _inputs(self, latents, timesteps, context):
+        """Checked inputs -> (all time_emb_proj outputs [N, sum Cout] fp32, the context's k|v per layer, context length, conv_in's output)."""
         cfg, dt, dev = self.cfg, self.dt, self.device
         if not latents.is_cuda or not context.is_cuda:
             raise RuntimeError("SdUnetEngine runs on a HIP device only (no CPU fallback)")
@@ -421,7 +426,20 @@ class SdUnetEngine(_Blocks):
         cp = self.conv_in.cin_p
         x = torch.empty((n, hh, ww, cp), dtype=tdt, device=dev)
         call("pmi_nchw_to_nhwc", ptr(latents), ptr(x), n, cin, hh, ww, cp, 1.0, 0.0, dt)
-        h = ops.igemm(x, self.conv_in, want_stats=True)
+        return emb, kv_all, tc, ops.igemm(x, self.conv_in, want_stats=True)
+
+    def _output(self, h, ca, cb):
+        cfg = self.cfg
+        n, hh, ww, _ = h.shape
+        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
+        out = torch.empty((n, cfg.out_channels, hh, ww), dtype=torch.float32, device=self.device)
+        call("pmi_nhwc_to_nchw", ptr(y), y.shape[-1], ptr(out), n, hh, ww, cfg.out_channels, 1.0, 0.0)
+        return out
+
+    @torch.no_grad()
+    def forward(self, latents: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor) -> torch.Tensor:
+        """latents NCHW fp32 [N, in, h, w], timesteps [N], context [N, T, context_dim] fp32 -> predicted noise NCHW fp32."""
+        emb, kv_all, tc, h = self._inputs(latents, timesteps, context)
         hs = [h]
         for blk in self.down:
             h = self._run(blk, h, None, emb, kv_all, tc)
@@ -429,11 +447,213 @@ class SdUnetEngine(_Blocks):
         h = self._run(self.mid, h, None, emb, kv_all, tc)
         for blk in self.up:
             h = self._run(blk, h, hs.pop(), emb, kv_all, tc)
-        ca, cb = ops.group_norm_coeffs(h, *self.gn_out, cfg.groups, dt)
-        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))
-        out = torch.empty((n, cfg.out_channels, hh, ww), dtype=torch.float32, device=dev)
-        call("pmi_nhwc_to_nchw", ptr(y), y.shape[-1], ptr(out), n, hh, ww, cfg.out_channels, 1.0, 0.0)
-        return out
+        ca, cb = ops.group_norm_coeffs(h, *self.gn_out, self.cfg.groups, self.dt)
+        return self._output(h, ca, cb)
+
+    # ---- input gradient (d loss / d latents through the frozen UNet: what autograd gives upstream when the latents require grad) ------------
+    # forward_train() issues forward()'s launch sequence and keeps what the nonlinear steps need.  Per ResnetBlock2D: its input(s), the GN1
+    # coefficients and partials, conv1's output, the GN2 ones.  Per transformer block: its input and GroupNorm, the fp32 token stream in front
+    # of each LayerNorm with mean_rstd, q|k|v / q with the attention output and log-sum-exp (flash route) or the softmax (kept-P route), and
+    # ff1's pre-GEGLU output.  Samplers keep nothing; the time embedding and the context's k|v are constants of the backward.
+    # The one launch that differs from forward(): ff1 runs without the fused GEGLU epilogue and pmi_geglu follows (the gate's input must
+    # exist in memory).  Where forward() fuses it (weights-direct GEMM), eps differs at rounding level: the fused form gates the fp32
+    # accumulator, the unfused one its 16-bit rounding; elsewhere forward_train() == forward() bit for bit.
+    flash_backward = True       # False: attention through the kept-P route (ops.attention_train / attention_backward), for the A/B
+
+    def _use_flash(self, c):
+        d = c // self.cfg.heads
+        return self.flash_backward and ops.FLASH_ENABLED and d <= 160 and d % 8 == 0
+
+    def _ln_train(self, x32, gb, m, c):
+        y = torch.empty((m, c), dtype=_hip.TORCH_DTYPE[self.dt], device=x32.device)
+        mr = torch.empty((2, m), dtype=torch.float32, device=x32.device)
+        call("pmi_layernorm_fwd", ptr(x32), c, ptr(gb[0]), ptr(gb[1]), ptr(y), None, ptr(mr), m, c, 1e-5, self.dt)
+        return y, mr
+
+    def _resnet_train(self, k, x, x1, nbias, tape):
+        dt, w, groups = self.dt, self.w, self.cfg.groups
+        ca, cb, p1 = ops.group_norm_coeffs_train(x, *w[k + ".gn1"], groups, dt, x1=x1)
+        h = ops.igemm(x, w[k + ".conv1"], a1=x1, nbias=nbias, prologue=(ca, cb, ACT_SILU), want_stats=True)
+        ca2, cb2, p2 = ops.group_norm_coeffs_train(h, *w[k + ".gn2"], groups, dt)
+        skip = ops.igemm(x, w[k + ".skip"], a1=x1) if (k + ".skip") in w else x
+        assert (k + ".skip") in w or x1 is None
+        tape.append(("res", k, x, x1, (ca, cb, p1), h, (ca2, cb2, p2)))
+        return ops.igemm(h, w[k + ".conv2"], residual=skip, prologue=(ca2, cb2, ACT_SILU), want_stats=True)
+
+    def _attn_train(self, k, x, kv_all, tc, tape):
+        dt, w, heads = self.dt, self.w, self.cfg.heads
+        n, hh, ww, c = x.shape
+        t, m, d = hh * ww, n * hh * ww, c // heads
+        b = k + ".transformer_blocks.0"
+        flash = self._use_flash(c)
+        ca, cb, parts = ops.group_norm_coeffs_train(x, *w[k + ".gn"], self.cfg.groups, dt, eps=1e-6)
+        hn = torch.empty_like(x)
+        call("pmi_gn_apply", ptr(x), None, c, ptr(ca), ptr(cb), None, ptr(hn), n, hh, ww, c, ACT_NONE, 0, dt)
+        h0 = ops.igemm(hn.view(m, c), w[k + ".proj_in"], out_f32=True)
+        z, mr1 = self._ln_train(h0, w[b + ".norm1"], m, c)
+        qkv = ops.igemm(z, w[b + ".qkv1"]).view(n, t, 3 * c)
+        if flash:
+            a, s1 = ops.flash_attention_train(qkv, qkv[..., c:], qkv[..., 2 * c:], heads, d, dt)
+        else:
+            a, pm = ops.attention_train(qkv, heads, dt)
+            s1 = (qkv, pm)
+        h1 = ops.igemm(a.view(m, c), w[b + ".out1"], residual=h0, out_f32=True)
+        z, mr2 = self._ln_train(h1, w[b + ".norm2"], m, c)
+        q = ops.igemm(z, w[b + ".q2"]).view(n, t, c)
+        kv = kv_all[b + ".kv2"].view(n, tc, 2 * c)
+        if flash:
+            a, s2 = ops.flash_attention_train(q, kv, kv[..., c:], heads, d, dt)
+        else:
+            a, pm = ops.cross_attention_train(q, kv, heads, dt)
+            s2 = (kv, pm)
+        h2 = ops.igemm(a.view(m, c), w[b + ".out2"], residual=h1, out_f32=True)
+        z, mr3 = self._ln_train(h2, w[b + ".norm3"], m, c)
+        f = ops.igemm(z, w[b + ".ff1"])                                             # pre-GEGLU, (16 value | 16 gate) column groups: kept
+        gg = torch.empty((m, 4 * c), dtype=f.dtype, device=f.device)
+        call("pmi_geglu", ptr(f), ptr(gg), m, 4 * c, 1, dt)
+        h16 = ops.igemm(gg, w[b + ".ff2"], residual=h2)
+        out = ops.igemm(h16, w[k + ".proj_out"], residual=x.view(m, c), want_stats=True, hw=t)
+        tape.append(("attn", k, x, (ca, cb, parts), (h0, mr1, s1), (h1, mr2, s2), (h2, mr3, f), flash))
+        return ops.view_nhwc(out, n, hh, ww)
+
+    def _run_train(self, blk, h, h1, emb, kv_all, tc, tape):
+        for l in blk:
+            if l[0] == "res":
+                off, co = self.emb_off[l[1]]
+                h = self._resnet_train(l[1], h, h1, emb[:, off:off + co], tape)
+            elif l[0] == "attn":
+                h = self._attn_train(l[1], h, kv_all, tc, tape)
+            elif l[0] == "down":
+                tape.append(("down", l[1]))
+                h = ops.igemm(h, self.w[l[1]], stride=2, want_stats=True)
+            else:
+                tape.append(("up", l[1]))
+                h = ops.igemm(h, self.w[l[1]], up=True, want_stats=True)
+            h1 = None
+        return h
+
+    @torch.no_grad()
+    def forward_train(self, latents: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor):
+        """As forward(), keeping what backward() needs: (predicted noise NCHW fp32, tape)."""
+        emb, kv_all, tc, h = self._inputs(latents, timesteps, context)
+        tape = {"down": [], "mid": [], "up": [], "in_shape": tuple(latents.shape)}
+        hs = [h]
+        for blk in self.down:
+            tp = []
+            h = self._run_train(blk, h, None, emb, kv_all, tc, tp)
+            tape["down"].append(tp)
+            hs.append(h)
+        h = self._run_train(self.mid, h, None, emb, kv_all, tc, tape["mid"])
+        for blk in self.up:
+            tp = []
+            h = self._run_train(blk, h, hs.pop(), emb, kv_all, tc, tp)
+            tape["up"].append(tp)
+        ca, cb, parts = ops.group_norm_coeffs_train(h, *self.gn_out, self.cfg.groups, self.dt)
+        tape["last"] = (h, (ca, cb, parts))
+        out = self._output(h, ca, cb)
+        tape["out_shape"] = tuple(out.shape)
+        return out, tape
+
+    def _res_back(self, rec, g, sd):
+        _, k, x, x1, gn1, h, gn2 = rec
+        dt, w, dev, groups = self.dt, self.w, self.device, self.cfg.groups
+        d_a2 = ops.igemm(g, ops.packed_dx(w, k + ".conv2T", sd[k + ".conv2.weight"], dt, dev))                  # wrt SiLU(GN2(h))
+        dh, _ = ops.group_norm_backward(h, d_a2, *gn2, w[k + ".gn2"][0], groups, dt, act=ACT_SILU)
+        d_a1 = ops.igemm(dh, ops.packed_dx(w, k + ".conv1T", sd[k + ".conv1.weight"], dt, dev))                 # wrt SiLU(GN1(cat(x, x1)))
+        gs0, gs1 = g, None
+        if (k + ".skip") in w:
+            skw = sd[k + ".conv_shortcut.weight"]
+            if x1 is None:
+                gs0 = ops.igemm(g, ops.packed_dx(w, k + ".skipT", skw, dt, dev))
+            else:
+                c0 = x.shape[-1]
+                gs0 = ops.igemm(g, ops.packed_dx(w, k + ".skipT0", skw[:, :c0], dt, dev))
+                gs1 = ops.igemm(g, ops.packed_dx(w, k + ".skipT1", skw[:, c0:], dt, dev))
+        return ops.group_norm_backward(x, d_a1, *gn1, w[k + ".gn1"][0], groups, dt, x1=x1, act=ACT_SILU, gadd0=gs0, gadd1=gs1)
+
+    def _ln_back(self, dy32, x32, gb, mr, gres, m, c):
+        """(fp32, 16-bit) gradient wrt the token stream in front of a LayerNorm: LayerNorm backward of dy32 plus gres, the gradient that
+        reaches the same stream through the residual connection."""
+        g32 = torch.empty((m, c), dtype=torch.float32, device=x32.device)
+        g16 = torch.empty((m, c), dtype=_hip.TORCH_DTYPE[self.dt], device=x32.device)
+        call("pmi_layernorm_bwd", ptr(dy32), ptr(x32), ptr(gb[0]), ptr(mr), ptr(gres), ptr(g32), ptr(g16), m, c, c, 1, self.dt)
+        return g32, g16
+
+    def _attn_back(self, rec, g, sd):
+        _, k, x, gn, (h0, mr1, s1), (h1, mr2, s2), (h2, mr3, f), flash = rec
+        dt, w, dev, heads = self.dt, self.w, self.device, self.cfg.heads
+        n, hh, ww, c = x.shape
+        t, m, d = hh * ww, n * hh * ww, c // heads
+        b = k + ".transformer_blocks.0"
+        T = lambda key, wt: ops.packed_dx(w, key, wt, dt, dev)
+        g = g.contiguous()
+        gh32 = ops.igemm(g.view(m, c), T(k + ".proj_outT", sd[k + ".proj_out.weight"]), out_f32=True)          # wrt ff2's output = wrt h2 (residual)
+        gh16 = torch.empty((m, c), dtype=g.dtype, device=dev)
+        call("pmi_cast_f32_to_16", ptr(gh32), ptr(gh16), gh32.numel(), ACT_NONE, dt)
+        d_gg = ops.igemm(gh16, T(b + ".ff2T", sd[b + ".ff.net.2.weight"]))
+        d_f = ops.geglu_backward(f, d_gg, dt)
+        if b + ".ff1T" not in w:
+            T(b + ".ff1T", ops.interleave_geglu(sd[b + ".ff.net.0.proj.weight"].detach().cpu().float(), None)[0])
+        d_z = ops.igemm(d_f, w[b + ".ff1T"], out_f32=True)
+        gh32, gh16 = self._ln_back(d_z, h2, w[b + ".norm3"], mr3, gh32, m, c)                                    # wrt h2
+        d_a = ops.igemm(gh16, T(b + ".out2T", sd[b + ".attn2.to_out.0.weight"])).view(n, t, c)
+        dq = ops.flash_attention_backward(s2, d_a, heads, d, dt, dq_only=True) if flash else ops.cross_attention_backward(s2[0], s2[1], d_a, heads, dt)
+        d_z = ops.igemm(dq.view(m, c), T(b + ".q2T", sd[b + ".attn2.to_q.weight"]), out_f32=True)
+        gh32, gh16 = self._ln_back(d_z, h1, w[b + ".norm2"], mr2, gh32, m, c)                                    # wrt h1
+        d_a = ops.igemm(gh16, T(b + ".out1T", sd[b + ".attn1.to_out.0.weight"])).view(n, t, c)
+        dqkv = ops.flash_attention_backward(s1, d_a, heads, d, dt) if flash else ops.attention_backward(s1[0], s1[1], d_a, heads, dt)
+        if b + ".qkv1T" not in w:
+            T(b + ".qkv1T", torch.cat([sd[f"{b}.attn1.{nm}.weight"].detach().cpu().float() for nm in ("to_q", "to_k", "to_v")], 0))
+        d_z = ops.igemm(dqkv.view(m, 3 * c), w[b + ".qkv1T"], out_f32=True)
+        gh32, gh16 = self._ln_back(d_z, h0, w[b + ".norm1"], mr1, gh32, m, c)                                    # wrt h0
+        d_hn = ops.igemm(gh16, T(k + ".proj_inT", sd[k + ".proj_in.weight"])).view(n, hh, ww, c)
+        gx, _ = ops.group_norm_backward(x, d_hn, *gn, w[k + ".gn"][0], self.cfg.groups, dt, act=ACT_NONE, gadd0=g, eps=1e-6)
+        return gx
+
+    def _back(self, tp, g, sd):
+        """Gradient wrt the input(s) of the layers recorded in `tp` from g = gradient wrt their output: (g_in, g_skip or None)."""
+        g1 = None
+        for rec in reversed(tp):
+            assert g1 is None
+            if rec[0] == "res":
+                g, g1 = self._res_back(rec, g, sd)
+            elif rec[0] == "attn":
+                g = self._attn_back(rec, g, sd)
+            elif rec[0] == "up":
+                g = self._up_back(rec[1], g, sd)
+            else:      # stride-2 convolution: dX = stride-1 convolution of the zero-inserted gradient with the flipped weights
+                n, h_, w_, c = g.shape
+                z = torch.zeros((n, 2 * h_, 2 * w_, c), dtype=g.dtype, device=g.device)
+                z[:, ::2, ::2] = g
+                g = ops.igemm(z, ops.packed_dx(self.w, rec[1] + "T", sd[rec[1] + ".weight"], self.dt, self.device))
+        return g, g1
+
+    @torch.no_grad()
+    def backward(self, tape, d_eps: torch.Tensor, state_dict) -> torch.Tensor:
+        """d loss / d latents (NCHW fp32 [N, in, h, w]) from d loss / d eps (NCHW fp32, forward_train()'s output shape) and its tape.
+        `state_dict`: the UNet's tensors by name (StableDiffusion.unet.state_dict()); transposed / folded weights are packed from it on first
+        use and kept on the engine.  Timesteps and context get no gradient.  f16 engines scale the gradient by a power of two on the way in
+        and back on the way out (ops.grad_to_nhwc); bf16 needs no scaling."""
+        cfg, dt, dev, w = self.cfg, self.dt, self.device, self.w
+        if not d_eps.is_cuda:
+            raise RuntimeError("SdUnetEngine runs on a HIP device only (no CPU fallback)")
+        if tuple(d_eps.shape) != tape["out_shape"]:
+            raise ValueError(f"d_eps must have the output's shape {tape['out_shape']}, got {tuple(d_eps.shape)}")
+        sd = {k: v.detach() for k, v in state_dict.items()}
+        g, gscale = ops.grad_to_nhwc(d_eps, dt, dev)
+        h, gn = tape["last"]
+        d_act = ops.igemm(g, ops.packed_dx(w, "conv_outT", sd["conv_out.weight"], dt, dev, cin_pad=8))
+        g, _ = ops.group_norm_backward(h, d_act, *gn, self.gn_out[0], cfg.groups, dt, act=ACT_SILU)
+        g_hs = []                                               # gradients of the skip tensors: the last up block read hs[0], ...
+        for tp in reversed(tape["up"]):
+            g, gk = self._back(tp, g, sd)
+            g_hs.append(gk)
+        g, _ = self._back(tape["mid"], g, sd)
+        for i in range(len(tape["down"]) - 1, -1, -1):          # hs[i + 1], the output of down block i, feeds the next block AND an up block
+            g, _ = self._back(tape["down"][i], ops.add2(g, g_hs[i + 1], dt), sd)
+        g = ops.add2(g, g_hs[0], dt)
+        gx = ops.igemm(g, ops.packed_dx(w, "conv_inT", sd["conv_in.weight"], dt, dev, rows=self.conv_in.cin_p), out_f32=True)
+        return ops.grad_to_nchw(gx, cfg.in_channels, 1.0 / gscale)
 
 
 class VaeDecoderEngine(_Blocks):
@@ -552,13 +772,6 @@ class VaeDecoderEngine(_Blocks):
         tape = {"rec": rec, "last": (h, (ca, cb, parts)), "scale": float(scale), "to_images": bool(to_images),
                 "in_shape": tuple(latents.shape), "out_shape": tuple(out.shape)}
         return out, tape
-
-    def _up_back(self, k, g, sd):
-        """Gradient wrt the input of nearest-x2 + conv3x3 from g = gradient wrt its output [N, 2h, 2w, C]: one stride-2 pass on the
-        phase-folded weights, faster at all three SD-v1 shapes than dX at the high resolution + the 2x2 sum (DESIGN.md §11)."""
-        if k + ".fold" not in self.w:
-            self.w[k + ".fold"] = PackedLinear(fold_upsample_weights(sd[k + ".weight"].cpu()).float(), None, self.dt, self.device)
-        return ops.igemm(g, self.w[k + ".fold"], stride=2)
 
     def _res_back(self, rec, g, sd, groups, eps):
         _, k, x, gn1, h, gn2 = rec

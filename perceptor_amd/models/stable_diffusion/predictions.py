@@ -12,6 +12,30 @@ from ...engine import sampler
 from ...utils.record import FrozenRecord
 
 
+class _Lincomb2(torch.autograd.Function):
+    """ca[n] * a + cb[n] * b (pmi_lincomb2) with gradients to a and b: ca[n] * g and cb[n] * g, the same kernel."""
+
+    @staticmethod
+    def forward(ctx, a, b, ca, cb):
+        ctx.coef = (ca, cb)
+        return sampler.lincomb2(a, ca, b, cb)
+
+    @staticmethod
+    def backward(ctx, g):
+        ca, cb = ctx.coef
+        g = g.float().contiguous()
+        return (sampler.lincomb2(g, ca) if ctx.needs_input_grad[0] else None, sampler.lincomb2(g, cb) if ctx.needs_input_grad[1] else None,
+                None, None)
+
+
+def _lincomb2(a, ca, b, cb):
+    """sampler.lincomb2, differentiable in a and b when grad mode is on and either requires grad (the UNet's input gradient reaches
+    from_diffused_latents through predicted_noise); otherwise the plain launch."""
+    if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+        return _Lincomb2.apply(a, b, ca, cb)
+    return sampler.lincomb2(a, ca, b, cb)
+
+
 class Predictions(FrozenRecord):
     _fields = ("from_diffused_latents", "from_indices", "predicted_noise", "schedule_alphas", "schedule_sigmas", "encode", "decode")
 
@@ -55,7 +79,7 @@ class Predictions(FrozenRecord):
     def denoised_latents(self):
         # (x - sigma*eps) / max(alpha, 1e-7)                                predictions.py:51-54
         a = self._a(self.from_indices).clamp(min=1e-7)
-        return sampler.lincomb2(self.from_diffused_latents, 1.0 / a, self.predicted_noise, -self._s(self.from_indices) / a)
+        return _lincomb2(self.from_diffused_latents, 1.0 / a, self.predicted_noise, -self._s(self.from_indices) / a)
 
     @property
     def denoised_images(self):

@@ -58,6 +58,25 @@ class _Decode(torch.autograd.Function):
         return g, None
 
 
+class _PredictedNoise(torch.autograd.Function):
+    """predicted_noise(x) with an input gradient, as autograd provides upstream through the UNet call under autocast
+    (stable_diffusion.py:259-271): forward and backward are the HIP UNet's forward_train / backward (engine/sd.py).  The UNet is frozen and
+    the timesteps and prompt encodings are constants: the UNet input is the only differentiable argument."""
+
+    @staticmethod
+    def forward(ctx, x, idx, enc, model):
+        eng = model._engine("unet")
+        eps, tape = eng.forward_train(x, idx, enc)
+        ctx.model, ctx.engine, ctx.tape = model, eng, tape
+        return eps
+
+    @staticmethod
+    def backward(ctx, grad_eps):
+        g = ctx.engine.backward(ctx.tape, grad_eps.float().contiguous(), ctx.model.unet.state_dict())
+        ctx.tape = None
+        return g, None, None, None
+
+
 class StableDiffusion(torch.nn.Module):
     """Loss-guided sampling: ``decode`` is differentiable with respect to the latents when grad mode is on and they require grad, so any
     image loss reaches the UNet's latent space as upstream::
@@ -67,7 +86,12 @@ class StableDiffusion(torch.nn.Module):
         loss(sd.decode(dl)).backward()
         diffused_latents = pred.guided(dl.grad).step(to_index)
 
-    Otherwise ``decode`` runs the no-grad decoder (no tape, same bits)."""
+    Otherwise ``decode`` runs the no-grad decoder (no tape, same bits).
+
+    ``predicted_noise`` / ``predictions`` / ``predictions_pair`` are differentiable in the diffused latents in the same way (grad mode on and
+    the latents require grad): ``pred.predicted_noise`` and ``pred.denoised_latents`` then carry the UNet's input gradient, e.g. for
+    ``guided_resample_``-style or score-distillation losses.  Timesteps and ``conditioning.encodings`` get no gradient; the weights are
+    frozen.  Without ``requires_grad`` (or under ``torch.no_grad()``) nothing changes: the no-grad UNet, no tape, same bits."""
 
     def __init__(self, name: str = "runwayml/stable-diffusion-v1-5", decoder_name: Optional[str] = "stabilityai/sd-vae-ft-mse",
                  fp16: bool = True, auth_token=True, flash_attention: bool = True, attention_slicing=None, *,
@@ -242,6 +266,11 @@ class StableDiffusion(torch.nn.Module):
         enc = conditioning.encodings
         if enc.shape[0] == 1 and n > 1:
             enc = enc.expand(n, -1, -1).contiguous()
+        return self._unet(x, idx, enc)
+
+    def _unet(self, x, idx, enc):
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _PredictedNoise.apply(x, idx, enc, self)
         return self._engine("unet").forward(x, idx, enc)
 
     def forward(self, diffused_latents, indices, conditioning: Optional[Conditioning] = None) -> Predictions:
@@ -270,7 +299,8 @@ class StableDiffusion(torch.nn.Module):
             self.__dict__["_pair_key"] = (ne, pe, ne._version, pe._version, n)
             self.__dict__["_pair_ctx"] = torch.cat([ex(neutral), ex(positive)], dim=0).contiguous()
         x = diffused_latents.to(self.device)
-        eps = self._engine("unet").forward(torch.cat([neutral.input(x), positive.input(x)], dim=0), torch.cat([idx, idx], dim=0), self._pair_ctx)
+        # under grad ONE 2N-sample tape: autograd's cat / slices give the latents the sum of both halves' gradients
+        eps = self._unet(torch.cat([neutral.input(x), positive.input(x)], dim=0), torch.cat([idx, idx], dim=0), self._pair_ctx)
         mk = lambda e: Predictions(from_diffused_latents=diffused_latents, from_indices=idx, predicted_noise=e.contiguous(),
                                    schedule_alphas=self.schedule_alphas, schedule_sigmas=self.schedule_sigmas, encode=self.encode, decode=self.decode)
         return mk(eps[:n]), mk(eps[n:])
