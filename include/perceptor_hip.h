@@ -111,7 +111,8 @@ int pmi_igemm_stats_rows(const pmi_igemm_args* a);
  * key 13 = allow its first-convolution form, tile config 8 (at most 32 input channels, the whole K in registers) (default 1);
  * key 9 = query-tile rows per wave of pmi_attn_flash (0 = automatic); key 10 = allow split-K in the weights-direct conv3x3 (default 1);
  * key 11 = largest split-K factor of the weights-direct GEMM (default 8); key 12 = workgroup count below which that GEMM uses its
- * 128-column tiles (default 128).  `python bench.py --opt "k=v,..."` sets them for a same-box A/B.
+ * 128-column tiles (default 128); key 14 = most query chunks per key tile of pmi_attn_flash_bwd_kv (0 = automatic, 1 = the unsplit key role).
+ * `python bench.py --opt "k=v,..."` sets them for a same-box A/B.
  * The library links no vendor GEMM / BLAS: every kernel it launches is in csrc/. */
 int pmi_set_option(int key, int value);
 
@@ -187,6 +188,18 @@ int pmi_attn_flash_bwd_workspace(int N, int T, int Tk, int heads, int d, int dq_
 int pmi_attn_flash_bwd(const void* q, int ldq, const void* k, const void* v, int ldkv, const void* out, const void* dout, const void* ws,
                        const float* lse, void* ws_bwd, float* delta, void* dq, int lddq, void* dk, void* dv, int lddkv, int N, int T, int Tk,
                        int heads, int d, float scale, int dq_only, int dtype, pmi_stream_t s);
+/* Cross-attention with a differentiable prompt (conditioning.encodings.requires_grad_(), stable_diffusion.py:259-271): dq as
+ * pmi_attn_flash_bwd(dq_only = 1) writes it, bit for bit, and dk / dv [N][Tk][lddkv] in FP32 (16-byte aligned, lddkv % 4 == 0), head h at
+ * channel offset h*d.  For Tk << T one wave per key tile would walk all of T alone: the query tiles are cut into
+ * S = pmi_attn_flash_bwd_kv_chunks(...) chunks, a function of the shape only; every (key tile, chunk) leaves an fp32 partial tile in ws_bwd
+ * and a second launch adds the S partials of each element in chunk order.  No atomics: run-to-run bit-identical.
+ * ws_bwd: pmi_attn_flash_bwd_kv_workspace(...) KiB.  S follows pmi_set_option key 14: the option must not change between the
+ * workspace query and the launch it sizes (a larger S would write partial tiles past the workspace). */
+int pmi_attn_flash_bwd_kv_chunks(int N, int T, int Tk, int heads, int d);
+int pmi_attn_flash_bwd_kv_workspace(int N, int T, int Tk, int heads, int d);
+int pmi_attn_flash_bwd_kv(const void* q, int ldq, const void* k, const void* v, int ldkv, const void* out, const void* dout, const void* ws,
+                          const float* lse, void* ws_bwd, float* delta, void* dq, int lddq, float* dk, float* dv, int lddkv, int N, int T,
+                          int Tk, int heads, int d, float scale, int dtype, pmi_stream_t s);
 int pmi_qkv_split(const void* qkv, void* q, void* k, void* vt, int N, int T, int heads, int order, int dtype, pmi_stream_t s);
 int pmi_attn_d64(const void* q, const void* k, const void* vt, void* out, int N, int T, int heads, float scale,
                  int dtype, pmi_stream_t s);

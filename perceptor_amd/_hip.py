@@ -81,6 +81,9 @@ _PROTOS = {
     "pmi_attn_flash_train": ([_P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],),
     "pmi_attn_flash_bwd_workspace": ([_I, _I, _I, _I, _I, _I],),
     "pmi_attn_flash_bwd": ([_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],),
+    "pmi_attn_flash_bwd_kv_chunks": ([_I, _I, _I, _I, _I],),
+    "pmi_attn_flash_bwd_kv_workspace": ([_I, _I, _I, _I, _I],),
+    "pmi_attn_flash_bwd_kv": ([_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P],),
     "pmi_qkv_split": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],),
     "pmi_attn_d64": ([_P, _P, _P, _P, _I, _I, _I, _F, _I, _P],),
     "pmi_vit_attn_fwd": ([_P, _P, _P, _P, _I, _I, _I, _F, _I, _P],),

@@ -327,8 +327,8 @@ int dispatch_flash(const u16* qf, const u16* kf, const u16* vtf, u16* out, float
 //               lane-local); dS^T, still in the accumulator, is the B operand of dQ^T += K^T dS^T.
 //   dK/dV role: one wave per 32-key tile, loops over query tiles.   S = Q K^T and dP = dO V^T put the key on the lane; P and dS are the B
 //               operands of dV^T += dO^T P and dK^T += Q^T dS.
-// Both roles of a layer are one launch (workgroups [0, ntk) own key tiles, the rest query tiles); cross-attention compiles the dQ role
-// alone.  Every output element is written once by one wave in a fixed order: run-to-run bit-identical.
+// Both roles of a layer are one launch (workgroups [0, ntk) own key tiles, the rest query tiles); cross-attention with a frozen
+// prompt compiles the dQ role alone, with a differentiable prompt the split key role further down.  Every output element is written once by one wave in a fixed order: run-to-run bit-identical.
 // Extra fragments (flash_bwd_split_kernel): dO and V in Q / K order, K^T (and, with dK / dV, dO^T and Q^T) in V^T order;
 // delta[bh][t] = sum_c dO[t][c] O[t][c] fp32.  P = exp2(S scale log2e - lse): lse is in the exp2 domain, as the forward's running maximum.
 template <typename T_>
@@ -509,6 +509,183 @@ struct FlashBwdArgs {
   float sl2, scale;
 };
 
+// ---- dK / dV for a short key sequence (cross-attention onto the prompt: Tk = 77 is three key tiles) ----------------------------------------
+// One wave per key tile walking every query tile leaves 3 N heads one-wave workgroups, each serial in T.  Here the query tiles are cut
+// into S chunks of L tiles: workgroup (key tile, chunk, sample x head) runs the key role over its chunk and leaves its fp32 accumulators
+// as a partial tile; flash_kv_reduce_kernel, a launch of its own (the kernel boundary makes the partials visible across the per-XCD L2s),
+// adds the S partials of every element in chunk order and writes fp32 dK | dV once.  No atomics; S depends on the shape alone
+// (flash_kv_chunks), so two runs are bit-identical.  S = 1: the accumulators go straight to dK | dV, the unsplit role's arithmetic.
+// dK / dV stay fp32: they sum up to T terms whose size no 16-bit range argument covers (dK = dS^T Q has no bound in terms of dO), and the
+// fp32 GEMM onto the prompt encodings takes them as they are.
+// Partial tile of (bh, key tile, chunk): [dK | dV][db][4 row groups][64 lanes] float4 = the accumulator registers, lane-contiguous.
+// flash_dkdv_body's loop over the query tiles [tb0, tb1) only, the accumulators handed back: dV^T += dO^T P and dK^T += Q^T dS into gv / gk
+// (zeroed here).  A function of its own so that the self-attention kernels above compile to exactly what they were.
+template <typename T_, int KQ, int DB>
+__device__ __forceinline__ void flash_dkdv_accumulate(const u16* __restrict__ qf, const u16* __restrict__ dof, const u16* __restrict__ kf,
+                                                      const u16* __restrict__ vf, const u16* __restrict__ qtf, const u16* __restrict__ dotf,
+                                                      const float* __restrict__ lse, const float* __restrict__ delta, int T, int Tk, float sl2,
+                                                      float scale, int bx, int bh, int tb0, int tb1, f32x16* gk, f32x16* gv) {
+  const int lane = threadIdx.x, l31 = lane & 31, lhi = lane >> 5;
+  const int ntq = (T + 31) >> 5, ntk = (Tk + 31) >> 5;
+  uint4 kr[KQ], vr[KQ];
+#pragma unroll
+  for (int kk = 0; kk < KQ; ++kk) {
+    kr[kk] = *(const uint4*)(kf + rfrag_g((int64_t)bh * ntk + bx, KQ, kk, lhi, l31));
+    vr[kk] = *(const uint4*)(vf + rfrag_g((int64_t)bh * ntk + bx, KQ, kk, lhi, l31));
+  }
+  const bool key_ok = bx * 32 + l31 < Tk;
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { gk[db][r] = 0.f; gv[db][r] = 0.f; }
+  for (int tb = tb0; tb < tb1; ++tb) {
+    const int64_t blk = (int64_t)bh * ntq + tb;
+    // the 16 query rows of this lane's accumulator registers: 4 runs of 4 consecutive rows
+    float4 ls[4], dl[4];
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+      ls[g4] = *(const float4*)(lse + blk * 32 + 8 * g4 + 4 * lhi);
+      dl[g4] = *(const float4*)(delta + blk * 32 + 8 * g4 + 4 * lhi);
+    }
+    f32x16 sacc, dp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+    for (int kk = 0; kk < KQ; ++kk) {
+      sacc = T_::mfma32(*(const uint4*)(qf + rfrag_g(blk, KQ, kk, lhi, l31)), kr[kk], sacc);        // rows = queries, lane = key
+      dp = T_::mfma32(*(const uint4*)(dof + rfrag_g(blk, KQ, kk, lhi, l31)), vr[kk], dp);
+    }
+    const bool tail = (tb + 1) * 32 > T;
+    float pf[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float* l4 = (const float*)&ls[r >> 2];
+      const float* d4 = (const float*)&dl[r >> 2];
+      float p = key_ok ? exp2f(fmaf(sacc[r], sl2, -l4[r & 3])) : 0.f;
+      if (tail && tb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi >= T) p = 0.f;
+      pf[r] = p;
+      sacc[r] = p * (dp[r] - d4[r & 3]) * scale;                                                     // dS[t][s]
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const uint4 pfrag = pack8<T_>(pf + 8 * ks);
+      float f[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = sacc[8 * ks + j];
+      const uint4 dsf = pack8<T_>(f);
+#pragma unroll
+      for (int db = 0; db < DB; ++db) {
+        gv[db] = T_::mfma32(*(const uint4*)(dotf + tfrag_g(blk, DB, ks, db, lhi, l31)), pfrag, gv[db]);
+        gk[db] = T_::mfma32(*(const uint4*)(qtf + tfrag_g(blk, DB, ks, db, lhi, l31)), dsf, gk[db]);
+      }
+    }
+  }
+}
+
+template <int DB>
+__device__ __forceinline__ void store_rows_f32(const f32x16* acc, float* dst, int d, int lhi) {
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int c = 32 * db + 8 * g + 4 * lhi;
+      if (c < d) *(float4*)(dst + c) = make_float4(acc[db][4 * g], acc[db][4 * g + 1], acc[db][4 * g + 2], acc[db][4 * g + 3]);
+    }
+}
+
+struct FlashBwdKvArgs {
+  FlashBwdArgs b;
+  float *part, *dk32, *dv32;     // dk32 / dv32 [N][Tk][lddkv] fp32, head h at channel offset h*d
+  int S, L;                      // chunks per key tile, query tiles per chunk (S = ceil(ntq / L): no chunk is empty)
+};
+
+template <typename T_, int KQ, int DB>
+__global__ __launch_bounds__(64) void attn_flash_bwd_kv_kernel(const FlashBwdKvArgs ka) {
+  const FlashBwdArgs& a = ka.b;
+  const int nx = gridDim.x;
+  const int lin = xcd_remap(blockIdx.x + nx * blockIdx.y, nx * gridDim.y);     // a head's tiles on one XCD, as the forward
+  const int bh = lin / nx, bx = lin - bh * nx;
+  const int ntq = (a.T + 31) >> 5, ntk = (a.Tk + 31) >> 5, nkey = ntk * ka.S;
+  if (bx >= nkey) {
+    flash_dq_body<T_, KQ, DB>(a.qf, a.dof, a.kf, a.vf, a.ktf, a.lse, a.delta, a.dq, a.lddq, a.T, a.Tk, a.heads, a.d, a.sl2, a.scale, bx - nkey, bh);
+    return;
+  }
+  const int kt = bx / ka.S, ch = bx - kt * ka.S;
+  const int lane = threadIdx.x, l31 = lane & 31, lhi = lane >> 5;
+  f32x16 gk[DB], gv[DB];
+  flash_dkdv_accumulate<T_, KQ, DB>(a.qf, a.dof, a.kf, a.vf, a.qtf, a.dotf, a.lse, a.delta, a.T, a.Tk, a.sl2, a.scale, kt, bh, ch * ka.L,
+                                    min(ntq, (ch + 1) * ka.L), gk, gv);
+  if (ka.S == 1) {
+    const int s = kt * 32 + l31;
+    if (s >= a.Tk) return;
+    const int n = bh / a.heads, h = bh - n * a.heads;
+    const int64_t off = ((int64_t)n * a.Tk + s) * a.lddkv + h * a.d;
+    store_rows_f32<DB>(gk, ka.dk32 + off, a.d, lhi);
+    store_rows_f32<DB>(gv, ka.dv32 + off, a.d, lhi);
+    return;
+  }
+  float4* p = (float4*)ka.part + (((int64_t)bh * ntk + kt) * ka.S + ch) * (2 * DB * 4 * 64) + lane;
+#pragma unroll
+  for (int db = 0; db < DB; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      p[(db * 4 + g) * 64] = make_float4(gk[db][4 * g], gk[db][4 * g + 1], gk[db][4 * g + 2], gk[db][4 * g + 3]);
+      p[((DB + db) * 4 + g) * 64] = make_float4(gv[db][4 * g], gv[db][4 * g + 1], gv[db][4 * g + 2], gv[db][4 * g + 3]);
+    }
+}
+
+// one thread per float4 of a (bh, key tile) output tile: the S partials added in chunk order, then written once
+__global__ __launch_bounds__(256) void flash_kv_reduce_kernel(const float4* __restrict__ part, float* __restrict__ dk32, float* __restrict__ dv32,
+                                                              int lddkv, int64_t total, int Tk, int heads, int d, int DB, int S) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int per = 2 * DB * 4 * 64, ntk = (Tk + 31) >> 5;
+  const int64_t tile = i / per;                    // bh * ntk + kt
+  const int in = (int)(i - tile * per), lane = in & 63, g = (in >> 6) & 3, wdb = in >> 8, which = wdb / DB, db = wdb - which * DB;
+  const int bh = (int)(tile / ntk), kt = (int)(tile - (int64_t)bh * ntk);
+  const int s = kt * 32 + (lane & 31), c = 32 * db + 8 * g + 4 * (lane >> 5);
+  if (s >= Tk || c >= d) return;
+  const float4* p = part + tile * S * per + in;
+  float4 acc = p[0];
+  for (int ch = 1; ch < S; ++ch) {
+    const float4 v = p[(int64_t)ch * per];
+    acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+  }
+  const int n = bh / heads, h = bh - n * heads;
+  *(float4*)((which ? dv32 : dk32) + ((int64_t)n * Tk + s) * lddkv + h * d + c) = acc;
+}
+
+static int g_kv_chunks = 0;      // A/B switch (pmi_set_option 14): 0 = automatic, n > 0 = at most n chunks (1 = the unsplit key role)
+
+// Chunks per key tile, from the shape alone.  The unsplit role has ntk N heads waves; the chip has 1024 SIMDs and the key role's two
+// accumulator sets leave room for about two waves on each, so the target is 2048 key-role workgroups.  A chunk keeps at least 4 query
+// tiles: a partial tile is as many bytes as the fragments of one query tile, so the workspace traffic stays below a quarter of the reads
+// (T = 64, two query tiles, stays unsplit).
+void flash_kv_chunks(int N, int T, int Tk, int heads, int* S, int* L) {
+  const int64_t ntq = (T + 31) / 32, ntk = (Tk + 31) / 32, waves = ntk * N * heads;
+  int64_t want = (2048 + waves - 1) / waves;
+  if (want > ntq / 4) want = ntq / 4;
+  if (g_kv_chunks > 0 && want > g_kv_chunks) want = g_kv_chunks;
+  if (want < 1) want = 1;
+  *L = (int)((ntq + want - 1) / want);
+  *S = (int)((ntq + *L - 1) / *L);
+}
+
+template <typename T_>
+int dispatch_flash_bwd_kv(const FlashBwdKvArgs& ka, int N, hipStream_t st) {
+  const FlashBwdArgs& a = ka.b;
+  const int KQ = (a.d + 15) / 16, DB = (a.d + 31) / 32, ntq = (a.T + 31) / 32, ntk = (a.Tk + 31) / 32;
+  const dim3 grid(ntq + ntk * ka.S, N * a.heads);
+#define CASE(kq, db)                                                                                 \
+  if (KQ == kq && DB == db) {                                                                        \
+    hipLaunchKernelGGL((attn_flash_bwd_kv_kernel<T_, kq, db>), grid, dim3(64), 0, st, ka);           \
+    return PMI_OK;                                                                                   \
+  }
+  CASE(1, 1) CASE(2, 1) CASE(3, 2) CASE(4, 2) CASE(5, 3) CASE(6, 3) CASE(7, 4) CASE(8, 4) CASE(9, 5) CASE(10, 5)
+#undef CASE
+  return PMI_ERR_ARG;
+}
+
 template <typename T_, int KQ, int DB, bool DQ_ONLY>
 __global__ __launch_bounds__(64) void attn_flash_bwd_kernel(const FlashBwdArgs a) {
   const int nx = gridDim.x;
@@ -567,6 +744,7 @@ int flash_forward(const void* q, int ldq, const void* k, const void* v, int ldkv
 }  // namespace
 
 void pmi_attn_flash_qt(int v) { g_flash_qt = v; }
+void pmi_attn_flash_kv_chunks(int v) { g_kv_chunks = v; }
 
 extern "C" int pmi_attn_flash_workspace(int N, int T, int Tk, int heads, int d) {       // in KiB (every term is a multiple of 1 KiB)
   if (N <= 0 || T <= 0 || Tk <= 0 || heads <= 0 || d <= 0 || d > 160 || (d & 7)) return -1;
@@ -628,5 +806,67 @@ extern "C" int pmi_attn_flash_bwd(const void* q, int ldq, const void* k, const v
   const int rc = dtype == PMI_DT_BF16 ? dispatch_flash_bwd<BF16>(a, N, dq_only != 0, st) : dispatch_flash_bwd<F16>(a, N, dq_only != 0, st);
   if (rc != PMI_OK) return rc;
   PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_attn_flash_bwd_kv_chunks(int N, int T, int Tk, int heads, int d) {
+  if (N <= 0 || T <= 0 || Tk <= 0 || heads <= 0 || d <= 0 || d > 160 || (d & 7)) return -1;
+  int S, L;
+  flash_kv_chunks(N, T, Tk, heads, &S, &L);
+  return S;
+}
+
+extern "C" int pmi_attn_flash_bwd_kv_workspace(int N, int T, int Tk, int heads, int d) {       // in KiB: the fragments, then the fp32 partial tiles
+  const int base = pmi_attn_flash_bwd_workspace(N, T, Tk, heads, d, 0);
+  if (base < 0) return -1;
+  int S, L;
+  flash_kv_chunks(N, T, Tk, heads, &S, &L);
+  const int64_t DB = (d + 31) / 32, ntk = (Tk + 31) / 32;
+  const int64_t kib = base + (S > 1 ? (int64_t)N * heads * ntk * S * DB * 8 : 0);
+  return kib > 0x7fffffff ? -1 : (int)kib;
+}
+
+extern "C" int pmi_attn_flash_bwd_kv(const void* q, int ldq, const void* k, const void* v, int ldkv, const void* out, const void* dout,
+                                     const void* ws, const float* lse, void* ws_bwd, float* delta, void* dq, int lddq, float* dk, float* dv,
+                                     int lddkv, int N, int T, int Tk, int heads, int d, float scale, int dtype, pmi_stream_t s) {
+  if (!flash_args_ok(q, ldq, k, v, ldkv, N, T, Tk, heads, d, dtype) || !out || !dout || !ws || !lse || !ws_bwd || !delta || !dq ||
+      lddq < heads * d || (lddq & 3) || !dk || !dv || lddkv < heads * d || (lddkv & 3) || ((uintptr_t)dk & 15) || ((uintptr_t)dv & 15))
+    return PMI_ERR_ARG;
+  const int64_t KQ = (d + 15) / 16, DB = (d + 31) / 32, ntq = (T + 31) / 32, ntk = (Tk + 31) / 32, NH = (int64_t)N * heads;
+  FlashBwdKvArgs ka;
+  FlashBwdArgs& a = ka.b;
+  flash_kv_chunks(N, T, Tk, heads, &ka.S, &ka.L);
+  a.qf = (const u16*)ws;
+  a.kf = a.qf + NH * ntq * KQ * 512;
+  u16* dof = (u16*)ws_bwd;
+  u16* vf = dof + NH * ntq * KQ * 512;
+  u16* ktf = vf + NH * ntk * KQ * 512;
+  u16* dotf = ktf + NH * ntk * DB * 1024;
+  u16* qtf = dotf + NH * ntq * DB * 1024;
+  ka.part = (float*)(qtf + NH * ntq * DB * 1024);       // every term above is a multiple of 1 KiB
+  ka.dk32 = dk; ka.dv32 = dv;
+  hipStream_t st = (hipStream_t)s;
+  const dim3 sg((unsigned)(ntq > ntk ? ntq : ntk), (unsigned)NH);
+  if (dtype == PMI_DT_BF16)
+    hipLaunchKernelGGL(flash_bwd_split_kernel<BF16>, sg, dim3(256), 0, st, (const u16*)q, ldq, (const u16*)k, (const u16*)v, ldkv, (const u16*)out,
+                       (const u16*)dout, dof, vf, ktf, dotf, qtf, delta, T, Tk, heads, d, (int)KQ, (int)DB, 0);
+  else
+    hipLaunchKernelGGL(flash_bwd_split_kernel<F16>, sg, dim3(256), 0, st, (const u16*)q, ldq, (const u16*)k, (const u16*)v, ldkv, (const u16*)out,
+                       (const u16*)dout, dof, vf, ktf, dotf, qtf, delta, T, Tk, heads, d, (int)KQ, (int)DB, 0);
+  PMI_CHECK_LAUNCH();
+  a.dof = dof; a.vf = vf; a.ktf = ktf; a.dotf = dotf; a.qtf = qtf;
+  a.lse = lse; a.delta = delta;
+  a.dq = (u16*)dq; a.dk = nullptr; a.dv = nullptr;
+  a.lddq = lddq; a.lddkv = lddkv; a.T = T; a.Tk = Tk; a.heads = heads; a.d = d;
+  a.scale = scale; a.sl2 = scale * 1.4426950408889634f;
+  const int rc = dtype == PMI_DT_BF16 ? dispatch_flash_bwd_kv<BF16>(ka, N, st) : dispatch_flash_bwd_kv<F16>(ka, N, st);
+  if (rc != PMI_OK) return rc;
+  PMI_CHECK_LAUNCH();
+  if (ka.S > 1) {
+    const int64_t total = NH * ntk * 2 * DB * 4 * 64;
+    hipLaunchKernelGGL(flash_kv_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float4*)ka.part, dk, dv, lddkv, total,
+                       Tk, heads, d, (int)DB, ka.S);
+    PMI_CHECK_LAUNCH();
+  }
   return PMI_OK;
 }

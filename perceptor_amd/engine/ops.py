@@ -811,17 +811,30 @@ def flash_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, hea
     return out, (q, k, v, ws, lse, out)
 
 
-def flash_attention_backward(saved, d_out: torch.Tensor, heads: int, d: int, dt: int, dq_only: bool = False) -> torch.Tensor:
+def flash_attention_backward(saved, d_out: torch.Tensor, heads: int, d: int, dt: int, dq_only: bool = False):
     """Gradient of flash_attention_train from d loss / d out [N, T, heads*d] (pmi_attn_flash_bwd: P recomputed per tile from lse).
     Self-attention (q, k, v are the three slices of one qkv tensor): d qkv [N, T, 3C], channels (q|k|v, head, d).  dq_only (cross-attention,
-    constant k / v): dq [N, T, C] alone."""
+    constant k / v): dq [N, T, C] alone.  Cross-attention (k, v the two halves of one [N, Tk, 2C] tensor) without dq_only: (dq [N, T, C] 16-bit, the dq_only
+    bits, and dkv [N, Tk, 2C] FP32 in the layout of the forward's kv) through pmi_attn_flash_bwd_kv, the key role split over query chunks.
+    dkv stays fp32: it sums up to T terms and feeds an fp32 GEMM, so no 16-bit range argument is needed."""
     q, k, v, ws, lse, out = saved
     n, t = q.shape[:2]
     tk, c = k.shape[1], heads * d
     assert d_out.is_contiguous() and tuple(d_out.shape) == (n, t, c)
+    delta = torch.empty_like(lse)
+    # cross-attention: k | v are the two halves of one [N, Tk, 2C] tensor (the forward's kv), the layout dkv is returned in
+    if not dq_only and k.stride(1) == 2 * c and v.data_ptr() == k.data_ptr() + c * k.element_size():
+        kib = _hip.lib().pmi_attn_flash_bwd_kv_workspace(n, t, tk, heads, d)
+        if kib < 0:
+            raise ValueError(f"flash attention: unsupported head dim {d}")
+        wsb = _empty((kib * 512,), q.dtype, q.device)
+        g = _empty((n, t, c), q.dtype, q.device)
+        dkv = _empty((n, tk, 2 * c), torch.float32, q.device)
+        call("pmi_attn_flash_bwd_kv", ptr(q), q.stride(1), ptr(k), ptr(v), k.stride(1), ptr(out), ptr(d_out), ptr(ws), ptr(lse), ptr(wsb),
+             ptr(delta), ptr(g), c, ptr(dkv), dkv.data_ptr() + 4 * c, 2 * c, n, t, tk, heads, d, float(d) ** -0.5, dt)
+        return g, dkv
     kib = _hip.lib().pmi_attn_flash_bwd_workspace(n, t, tk, heads, d, int(dq_only))
     wsb = _empty((kib * 512,), q.dtype, q.device)
-    delta = torch.empty_like(lse)
     if dq_only:
         g = _empty((n, t, c), q.dtype, q.device)
         dk = dv = None
@@ -854,9 +867,10 @@ def cross_attention_train(q: torch.Tensor, kv: torch.Tensor, heads: int, dt: int
     return out, p
 
 
-def cross_attention_backward(kv: torch.Tensor, p: torch.Tensor, d_out: torch.Tensor, heads: int, dt: int) -> torch.Tensor:
-    """d loss / d q [N, T, C] of cross_attention_train from the kept softmax (k and v are constants of the backward): dP = dO V^T,
-    dS = softmax'(P, dP), dQ = dS K."""
+def cross_attention_backward(kv: torch.Tensor, p: torch.Tensor, d_out: torch.Tensor, heads: int, dt: int, q: Optional[torch.Tensor] = None):
+    """d loss / d q [N, T, C] of cross_attention_train from the kept softmax: dP = dO V^T, dS = softmax'(P, dP), dQ = dS K.  With q (the
+    forward's queries; a differentiable prompt) also d loss / d kv: (dq, dkv [N, Tc, 2C] fp32), dV = P^T dO and dK = dS^T Q through the same
+    batched GEMMs, fp32 out as flash_attention_backward's."""
     n, t, c = d_out.shape
     tc = kv.shape[1]
     d = c // heads
@@ -871,7 +885,19 @@ def cross_attention_backward(kv: torch.Tensor, p: torch.Tensor, d_out: torch.Ten
     dq = _empty((n, t, c), d_out.dtype, dev)
     bgemm(ds, kt, dq, M=t, N=d, K=tcp, lda=tcp, ldb=tcp, ldd=c, batch=n * heads, batch_inner=heads,
           sA=(heads * t * tcp, t * tcp), sB=(heads * d * tcp, d * tcp), sD=(t * c, d), dt=dt)
-    return dq
+    if q is None:
+        return dq
+    tp = (t + 7) // 8 * 8
+    dkv = _empty((n, tc, 2 * c), torch.float32, dev)
+    pt = _transpose16(p, 0, t, tc, tcp, heads * t * tcp, t * tcp, heads, n * heads)             # [N*heads, Tc, Tp]
+    dot = _transpose16(d_out, 0, t, d, c, t * c, d, heads, n * heads)                             # [N*heads, d, Tp]
+    bgemm(pt, dot, dkv, M=tc, N=d, K=tp, lda=tp, ldb=tp, ldd=2 * c, batch=n * heads, batch_inner=heads,
+          sA=(heads * tc * tp, tc * tp), sB=(heads * d * tp, d * tp), sD=(tc * 2 * c, d), dt=dt, d_off=c)          # dV
+    dst = _transpose16(ds, 0, t, tc, tcp, heads * t * tcp, t * tcp, heads, n * heads)
+    qt = _transpose16(q, 0, t, d, c, t * c, d, heads, n * heads)
+    bgemm(dst, qt, dkv, M=tc, N=d, K=tp, lda=tp, ldb=tp, ldd=2 * c, batch=n * heads, batch_inner=heads,
+          sA=(heads * tc * tp, tc * tp), sB=(heads * d * tp, d * tp), sD=(tc * 2 * c, d), dt=dt)                   # dK
+    return dq, dkv
 
 
 def geglu_backward(h: torch.Tensor, dg: torch.Tensor, dt: int) -> torch.Tensor:

@@ -536,7 +536,7 @@ class SdUnetEngine(_Blocks):
     def forward_train(self, latents: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor):
         """As forward(), keeping what backward() needs: (predicted noise NCHW fp32, tape)."""
         emb, kv_all, tc, h = self._inputs(latents, timesteps, context)
-        tape = {"down": [], "mid": [], "up": [], "in_shape": tuple(latents.shape)}
+        tape = {"down": [], "mid": [], "up": [], "in_shape": tuple(latents.shape), "ctx_shape": tuple(context.shape)}
         hs = [h]
         for blk in self.down:
             tp = []
@@ -579,7 +579,24 @@ class SdUnetEngine(_Blocks):
         call("pmi_layernorm_bwd", ptr(dy32), ptr(x32), ptr(gb[0]), ptr(mr), ptr(gres), ptr(g32), ptr(g16), m, c, c, 1, self.dt)
         return g32, g16
 
-    def _attn_back(self, rec, g, sd):
+    def _ctx_back(self, b, dkv, sd, cg):
+        """One cross-attention layer's share of d loss / d context: dkv [N, Tc, 2C] fp32 times (to_k | to_v) [2C, context_dim], added to the
+        running sum cg["acc"] in the GEMM's epilogue (layers in the backward's order: a fixed order).  All fp32 (csrc/f32gemm.hip): dK / dV sum
+        up to T = 4096 terms and dK = dS^T Q has no bound in terms of the cotangent, so no 16-bit hand-over can be argued free of overflow in
+        f16; an fp32 operand needs no argument.  The weights are the forward's 16-bit operands widened (the gradient of the function the
+        forward computes), kept on the engine like every transposed weight.  alpha divides the f16 cotangent scale out."""
+        key = b + ".kv2T"
+        if key not in self.w:
+            wkv = torch.cat([sd[b + ".attn2.to_k.weight"].to(self.device), sd[b + ".attn2.to_v.weight"].to(self.device)], 0)
+            self.w[key] = wkv.float().to(_hip.TORCH_DTYPE[self.dt]).float().contiguous()        # rounded on the device, once
+        wkv = self.w[key]
+        n, tc, c2 = dkv.shape
+        out = torch.empty((n * tc, wkv.shape[1]), dtype=torch.float32, device=self.device)
+        ops.gemm_f32(dkv, wkv, out, M=n * tc, N=wkv.shape[1], K=c2, lda=c2, ldb=wkv.shape[1], ldd=wkv.shape[1], trans_b=True,
+                     alpha=cg["mul"], residual=cg["acc"])
+        cg["acc"] = out
+
+    def _attn_back(self, rec, g, sd, cg=None):
         _, k, x, gn, (h0, mr1, s1), (h1, mr2, s2), (h2, mr3, f), flash = rec
         dt, w, dev, heads = self.dt, self.w, self.device, self.cfg.heads
         n, hh, ww, c = x.shape
@@ -597,7 +614,15 @@ class SdUnetEngine(_Blocks):
         d_z = ops.igemm(d_f, w[b + ".ff1T"], out_f32=True)
         gh32, gh16 = self._ln_back(d_z, h2, w[b + ".norm3"], mr3, gh32, m, c)                                    # wrt h2
         d_a = ops.igemm(gh16, T(b + ".out2T", sd[b + ".attn2.to_out.0.weight"])).view(n, t, c)
-        dq = ops.flash_attention_backward(s2, d_a, heads, d, dt, dq_only=True) if flash else ops.cross_attention_backward(s2[0], s2[1], d_a, heads, dt)
+        if cg is None:
+            dq = ops.flash_attention_backward(s2, d_a, heads, d, dt, dq_only=True) if flash else ops.cross_attention_backward(s2[0], s2[1], d_a, heads, dt)
+        else:
+            if flash:
+                dq, dkv = ops.flash_attention_backward(s2, d_a, heads, d, dt)
+            else:       # the kept-P tape holds no q (it stays what the latent-only backward keeps): the forward's two launches again, same bits
+                q = ops.igemm(self._ln(h1, w[b + ".norm2"], m, c), w[b + ".q2"]).view(n, t, c)
+                dq, dkv = ops.cross_attention_backward(s2[0], s2[1], d_a, heads, dt, q=q)
+            self._ctx_back(b, dkv, sd, cg)
         d_z = ops.igemm(dq.view(m, c), T(b + ".q2T", sd[b + ".attn2.to_q.weight"]), out_f32=True)
         gh32, gh16 = self._ln_back(d_z, h1, w[b + ".norm2"], mr2, gh32, m, c)                                    # wrt h1
         d_a = ops.igemm(gh16, T(b + ".out1T", sd[b + ".attn1.to_out.0.weight"])).view(n, t, c)
@@ -610,15 +635,16 @@ class SdUnetEngine(_Blocks):
         gx, _ = ops.group_norm_backward(x, d_hn, *gn, w[k + ".gn"][0], self.cfg.groups, dt, act=ACT_NONE, gadd0=g, eps=1e-6)
         return gx
 
-    def _back(self, tp, g, sd):
-        """Gradient wrt the input(s) of the layers recorded in `tp` from g = gradient wrt their output: (g_in, g_skip or None)."""
+    def _back(self, tp, g, sd, cg=None):
+        """Gradient wrt the input(s) of the layers recorded in `tp` from g = gradient wrt their output: (g_in, g_skip or None).
+        cg: the context gradient's running state (backward(cond_grad=True)), None when the prompt is a constant."""
         g1 = None
         for rec in reversed(tp):
             assert g1 is None
             if rec[0] == "res":
                 g, g1 = self._res_back(rec, g, sd)
             elif rec[0] == "attn":
-                g = self._attn_back(rec, g, sd)
+                g = self._attn_back(rec, g, sd, cg)
             elif rec[0] == "up":
                 g = self._up_back(rec[1], g, sd)
             else:      # stride-2 convolution: dX = stride-1 convolution of the zero-inserted gradient with the flipped weights
@@ -629,11 +655,13 @@ class SdUnetEngine(_Blocks):
         return g, g1
 
     @torch.no_grad()
-    def backward(self, tape, d_eps: torch.Tensor, state_dict) -> torch.Tensor:
+    def backward(self, tape, d_eps: torch.Tensor, state_dict, cond_grad: bool = False):
         """d loss / d latents (NCHW fp32 [N, in, h, w]) from d loss / d eps (NCHW fp32, forward_train()'s output shape) and its tape.
         `state_dict`: the UNet's tensors by name (StableDiffusion.unet.state_dict()); transposed / folded weights are packed from it on first
-        use and kept on the engine.  Timesteps and context get no gradient.  f16 engines scale the gradient by a power of two on the way in
-        and back on the way out (ops.grad_to_nhwc); bf16 needs no scaling."""
+        use and kept on the engine.  cond_grad=True: (d_latents, d_context), d_context fp32 [N, Tc, context_dim] = d loss / d context, the sum
+        over the cross-attention layers of (dK | dV) (to_k | to_v); d_latents has the bits of the cond_grad=False call.  Timesteps get no
+        gradient.  f16 engines scale the gradient by a power of two on the way in and back on the way out (ops.grad_to_nhwc), for both results;
+        bf16 needs no scaling."""
         cfg, dt, dev, w = self.cfg, self.dt, self.device, self.w
         if not d_eps.is_cuda:
             raise RuntimeError("SdUnetEngine runs on a HIP device only (no CPU fallback)")
@@ -641,19 +669,25 @@ class SdUnetEngine(_Blocks):
             raise ValueError(f"d_eps must have the output's shape {tape['out_shape']}, got {tuple(d_eps.shape)}")
         sd = {k: v.detach() for k, v in state_dict.items()}
         g, gscale = ops.grad_to_nhwc(d_eps, dt, dev)
+        cg = {"acc": None, "mul": 1.0 / gscale} if cond_grad else None
         h, gn = tape["last"]
         d_act = ops.igemm(g, ops.packed_dx(w, "conv_outT", sd["conv_out.weight"], dt, dev, cin_pad=8))
         g, _ = ops.group_norm_backward(h, d_act, *gn, self.gn_out[0], cfg.groups, dt, act=ACT_SILU)
         g_hs = []                                               # gradients of the skip tensors: the last up block read hs[0], ...
         for tp in reversed(tape["up"]):
-            g, gk = self._back(tp, g, sd)
+            g, gk = self._back(tp, g, sd, cg)
             g_hs.append(gk)
-        g, _ = self._back(tape["mid"], g, sd)
+        g, _ = self._back(tape["mid"], g, sd, cg)
         for i in range(len(tape["down"]) - 1, -1, -1):          # hs[i + 1], the output of down block i, feeds the next block AND an up block
-            g, _ = self._back(tape["down"][i], ops.add2(g, g_hs[i + 1], dt), sd)
+            g, _ = self._back(tape["down"][i], ops.add2(g, g_hs[i + 1], dt), sd, cg)
         g = ops.add2(g, g_hs[0], dt)
         gx = ops.igemm(g, ops.packed_dx(w, "conv_inT", sd["conv_in.weight"], dt, dev, rows=self.conv_in.cin_p), out_f32=True)
-        return ops.grad_to_nchw(gx, cfg.in_channels, 1.0 / gscale)
+        gx = ops.grad_to_nchw(gx, cfg.in_channels, 1.0 / gscale)
+        if not cond_grad:
+            return gx
+        if cg["acc"] is None:
+            raise RuntimeError("cond_grad: this UNet configuration has no cross-attention layer")
+        return gx, cg["acc"].view(tape["ctx_shape"])
 
 
 class VaeDecoderEngine(_Blocks):

@@ -59,22 +59,31 @@ class _Decode(torch.autograd.Function):
 
 
 class _PredictedNoise(torch.autograd.Function):
-    """predicted_noise(x) with an input gradient, as autograd provides upstream through the UNet call under autocast
+    """predicted_noise(x, encodings) with input gradients, as autograd provides upstream through the UNet call under autocast
     (stable_diffusion.py:259-271): forward and backward are the HIP UNet's forward_train / backward (engine/sd.py).  The UNet is frozen and
-    the timesteps and prompt encodings are constants: the UNet input is the only differentiable argument."""
+    the timesteps are integer indices: the UNet input and the prompt encodings are the differentiable arguments, and backward asks the
+    engine for exactly those that need a gradient."""
 
     @staticmethod
     def forward(ctx, x, idx, enc, model):
         eng = model._engine("unet")
-        eps, tape = eng.forward_train(x, idx, enc)
-        ctx.model, ctx.engine, ctx.tape = model, eng, tape
+        # differentiable encodings are usually edited between calls (an optimiser step, possibly through .data, which no version counter
+        # sees): the engine gets a copy of its own, so its k|v cache can never serve an older value of the same tensor
+        eps, tape = eng.forward_train(x, idx, enc.detach().clone() if ctx.needs_input_grad[2] else enc)
+        ctx.model, ctx.engine, ctx.tape, ctx.enc_dtype = model, eng, tape, enc.dtype
         return eps
 
     @staticmethod
     def backward(ctx, grad_eps):
-        g = ctx.engine.backward(ctx.tape, grad_eps.float().contiguous(), ctx.model.unet.state_dict())
+        need_x, need_enc = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        g_enc = None
+        if need_enc:
+            g, g_enc = ctx.engine.backward(ctx.tape, grad_eps.float().contiguous(), ctx.model.unet.state_dict(), cond_grad=True)
+            g_enc = g_enc.to(ctx.enc_dtype)
+        else:
+            g = ctx.engine.backward(ctx.tape, grad_eps.float().contiguous(), ctx.model.unet.state_dict())
         ctx.tape = None
-        return g, None, None, None
+        return (g if need_x else None), None, g_enc, None
 
 
 class StableDiffusion(torch.nn.Module):
@@ -90,8 +99,11 @@ class StableDiffusion(torch.nn.Module):
 
     ``predicted_noise`` / ``predictions`` / ``predictions_pair`` are differentiable in the diffused latents in the same way (grad mode on and
     the latents require grad): ``pred.predicted_noise`` and ``pred.denoised_latents`` then carry the UNet's input gradient, e.g. for
-    ``guided_resample_``-style or score-distillation losses.  Timesteps and ``conditioning.encodings`` get no gradient; the weights are
-    frozen.  Without ``requires_grad`` (or under ``torch.no_grad()``) nothing changes: the no-grad UNet, no tape, same bits."""
+    ``guided_resample_``-style or score-distillation losses.  They are differentiable in ``conditioning.encodings`` as well
+    (``conditioning.encodings.requires_grad_()``), alone or together with the latents: prompt-embedding optimisation, per-token prompt
+    weights, score distillation with a learned prompt; batch-1 encodings shared by N samples get the sum over the samples.  Timesteps get
+    no gradient (they are int64 indices upstream too); the weights are frozen.  With nothing requiring grad (or under ``torch.no_grad()``)
+    nothing changes: the no-grad UNet, no tape, same bits."""
 
     def __init__(self, name: str = "runwayml/stable-diffusion-v1-5", decoder_name: Optional[str] = "stabilityai/sd-vae-ft-mse",
                  fp16: bool = True, auth_token=True, flash_attention: bool = True, attention_slicing=None, *,
@@ -269,7 +281,7 @@ class StableDiffusion(torch.nn.Module):
         return self._unet(x, idx, enc)
 
     def _unet(self, x, idx, enc):
-        if torch.is_grad_enabled() and x.requires_grad:
+        if torch.is_grad_enabled() and (x.requires_grad or enc.requires_grad):
             return _PredictedNoise.apply(x, idx, enc, self)
         return self._engine("unet").forward(x, idx, enc)
 
@@ -295,12 +307,18 @@ class StableDiffusion(torch.nn.Module):
         # in-place version (an edited encodings tensor, e.g. prompt weighting, is a new context).
         ne, pe = neutral.encodings, positive.encodings
         key = self.__dict__.get("_pair_key")
-        if key is None or key[0] is not ne or key[1] is not pe or key[2:] != (ne._version, pe._version, n):
+        if torch.is_grad_enabled() and (ne.requires_grad or pe.requires_grad):
+            # differentiable encodings: the 2N-sample context is built inside the graph, so each prompt gets its own half of the gradient
+            # (the cached context is neither used nor replaced)
+            pair_ctx = torch.cat([ex(neutral), ex(positive)], dim=0).contiguous()
+        elif key is None or key[0] is not ne or key[1] is not pe or key[2:] != (ne._version, pe._version, n):
             self.__dict__["_pair_key"] = (ne, pe, ne._version, pe._version, n)
-            self.__dict__["_pair_ctx"] = torch.cat([ex(neutral), ex(positive)], dim=0).contiguous()
+            self.__dict__["_pair_ctx"] = pair_ctx = torch.cat([ex(neutral), ex(positive)], dim=0).contiguous()
+        else:
+            pair_ctx = self._pair_ctx
         x = diffused_latents.to(self.device)
         # under grad ONE 2N-sample tape: autograd's cat / slices give the latents the sum of both halves' gradients
-        eps = self._unet(torch.cat([neutral.input(x), positive.input(x)], dim=0), torch.cat([idx, idx], dim=0), self._pair_ctx)
+        eps = self._unet(torch.cat([neutral.input(x), positive.input(x)], dim=0), torch.cat([idx, idx], dim=0), pair_ctx)
         mk = lambda e: Predictions(from_diffused_latents=diffused_latents, from_indices=idx, predicted_noise=e.contiguous(),
                                    schedule_alphas=self.schedule_alphas, schedule_sigmas=self.schedule_sigmas, encode=self.encode, decode=self.decode)
         return mk(eps[:n]), mk(eps[n:])
