@@ -641,6 +641,84 @@ def gen_sd_ldm():
         save(f"sd_ldm_vae_{tag}", dec=y, mean=mom[:, :cfg.latent_channels], logvar=mom[:, cfg.latent_channels:], hw=np.array(hw), img_hw=np.array(img.shape[-1]))
 
 
+def _save_fullsize(name, y, x, seed, t, **extra):
+    """One full-size fixture: the output at the sampled positions of tests/_fullsize_ref.py, moments and float64 channel sums of the whole
+    output; of the input only its seed, shape and a float64 checksum (the tests rebuild it with seeded_noise and assert the checksum)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _fullsize_ref as FS
+    stride = FS.STRIDE[y.shape[-1]]
+    s = FS.sample(y, stride)
+    save(name, y_lat=s["lat"], y_rows=s["rows"], y_cols=s["cols"], y_mom=moments(y), ch_sum=FS.channel_sums(y), stride=np.array(stride),
+         x_seed=np.array(seed), x_shape=np.array(x.shape), x_chk=FS.checksum(x), t=t, **extra)
+
+
+def gen_fullsize_adm():
+    """The shipped 'standard' ADM UNet (558 M parameters) at the benchmark's sizes: 256x256 (C2) and 512x512 (C5)."""
+    cm = R.ref("models.guided_diffusion.create_models")
+    m, _ = cm.create_openimages_model()
+    m.convert_to_fp32()
+    m.dtype = torch.float32
+    m.eval()
+    m.load_state_dict(synth_like(m.state_dict(), 0))
+    for res, seed, t in ((256, 132, 617), (512, 133, 181)):
+        x = seeded_noise((1, 3, res, res), seed)
+        tt = torch.tensor([t])
+        with torch.no_grad():
+            y = m(x, tt)
+        _save_fullsize(f"adm_standard_{res}", y, x, seed, tt)
+
+
+def gen_fullsize_vdiff():
+    """YFCC2Model (968 M parameters) at 512x512 (C3) and the CLIP-conditioned CC12M1Model at 256x256 (C1)."""
+    y2 = R.ref("models.velocity_diffusion.yfcc_2")
+    cc = R.ref("models.velocity_diffusion.cc12m_1")
+    m = y2.YFCC2Model().eval()
+    m.load_state_dict(synth_like(m.state_dict(), 0))
+    x, t = seeded_noise((1, 3, 512, 512), 141), torch.tensor([0.55])
+    with torch.no_grad():
+        y = m(x, t)
+    _save_fullsize("vdiff_yfcc_2_512", y, x, 141, t)
+    del m, y
+    m = cc.CC12M1Model().eval()
+    m.load_state_dict(synth_like(m.state_dict(), 0))
+    x, t, ce = seeded_noise((1, 3, 256, 256), 142), torch.tensor([0.4]), seeded_noise((1, 512), 143)
+    with torch.no_grad():
+        y = m(x, t, ce)
+    _save_fullsize("vdiff_cc12m_1_256", y, x, 142, t, clip_embed=ce)
+
+
+def gen_fullsize_sd():
+    """The SD-v1 UNet (860 M parameters) as the reference's vendored ldm UNetModel at 64x64 latents (C4) with a 77-token context: the
+    4 x 64 x 64 output in full; latents and context by seed and checksum."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _fullsize_ref as FS
+    from oracle import sd as osd
+    from perceptor_amd.utils.synth import synth_state_dict
+    om = R.ref("models.latent_diffusion.ldm.modules.diffusionmodules.openaimodel")
+    cfg, hw, tc = osd.SD_V1, 64, 77
+    bo = cfg.block_out
+    m = om.UNetModel(image_size=hw, in_channels=cfg.in_channels, out_channels=cfg.out_channels, model_channels=bo[0],
+                     attention_resolutions=[2 ** i for i, c in enumerate(cfg.cross_attn) if c], num_res_blocks=cfg.layers_per_block,
+                     channel_mult=[c // bo[0] for c in bo], num_heads=cfg.heads, use_spatial_transformer=True, transformer_depth=1,
+                     context_dim=cfg.context_dim, use_checkpoint=False, legacy=False).eval()
+    m.load_state_dict(_ldm_unet_keys(cfg, synth_state_dict(osd.unet_state_dict_shapes(cfg), 0)), strict=True)
+    x, ctx = seeded_noise((1, cfg.in_channels, hw, hw), 171), seeded_noise((1, tc, cfg.context_dim), 172)
+    t = torch.tensor([437])
+    with torch.no_grad():
+        y = m(x, t, context=ctx)
+    save("sd_ldm_unet_v1_64", eps=y, y_mom=moments(y), ch_sum=FS.channel_sums(y), t=t, x_seed=np.array(171), x_shape=np.array(x.shape),
+         x_chk=FS.checksum(x), ctx_seed=np.array(172), ctx_shape=np.array(ctx.shape), ctx_chk=FS.checksum(ctx))
+
+
+def gen_fullsize():
+    """Outputs of the reference's own modules at the sizes the project is benchmarked on (BASELINE configs C1 ... C5), N = 1, fp32, no_grad,
+    name-keyed weights seed 0; seeds, timesteps and the clip embedding differ from the 64-128 px fixtures.  A few minutes and < 20 GB on
+    8 cores.  tools/gen_fullsize_floor64.py then adds each fixture's float64 noise floor F."""
+    gen_fullsize_adm()
+    gen_fullsize_vdiff()
+    gen_fullsize_sd()
+
+
 TOKENIZER_PROMPTS = [
     "a photograph of a playful cat", "painting of a dog", "", "  Hello,   World!  it's 2023 -- don't panic...",
     "An astronaut riding a horse on Mars; 4k, trending on artstation (highly detailed)", "fish &amp; chips &lt;3 #tasty @home 100% / 50$",

@@ -1,6 +1,6 @@
 """GPU: the benchmark's full-size workload (BASELINE.json configs[4] per-GPU share: GuidedDiffusion "standard" UNet at
-512x512, batch 8, OpenCLIP ViT-L/14 guidance, bf16) checked through size-independent properties -- the CPU oracle cannot run
-this size in test time, so instead of values the test pins what must hold at ANY size:
+512x512, batch 8, OpenCLIP ViT-L/14 guidance, bf16) checked through size-independent properties: what must hold at ANY size.  (Values at this size
+are pinned to the reference's own output in test_gpu_fullsize_reference.py, from fixtures the reference generated once on the CPU.)
 
   * determinism: the same inputs twice give bit-identical outputs (every reduction in the kernels has a fixed order);
   * chain independence (the basis of the replica sharding): permuting the batch permutes the outputs bit-exactly,
@@ -8,7 +8,8 @@ this size in test time, so instead of values the test pins what must hold at ANY
   * the fused sampler algebra at full size: x = denoised * alpha + eps * sigma reproduces the input (Predictions round trip,
     guided_diffusion/predictions.py:51-59), and a DDIM step to the same index is the identity;
   * everything finite, guidance gradient non-zero for every chain.
-Value parity for the same engines is pinned at 128x128 against the reference's golden vectors in test_gpu_adm.py / test_gpu_clip.py.
+Value parity for the same engines is pinned against the reference's golden vectors at 128x128 in test_gpu_adm.py / test_gpu_clip.py and at
+256x256 / 512x512, at the benchmark's batches, in test_gpu_fullsize_reference.py.
 """
 import pytest
 import torch

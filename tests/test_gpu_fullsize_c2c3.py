@@ -1,11 +1,13 @@
 """GPU: BASELINE.json configs[1] (C2: GuidedDiffusion 256x256, batch 4, no CLIP) and configs[2] (C3: VelocityDiffusion yfcc_2 512x512,
-batch 8 + OpenCLIP ViT-B/32 guidance) at FULL size, through size-independent properties (the CPU oracle needs minutes per sample here):
+batch 8 + OpenCLIP ViT-B/32 guidance) at FULL size, through size-independent properties and mode-against-mode distances (the same engines
+against the reference's own values at these sizes and batches: tests/test_gpu_fullsize_reference.py):
 
   * determinism and chain independence (bit-exact under a batch permutation);
   * the Predictions algebra round trips at full size (x = x0*alpha + eps*sigma; a step to the same level is the identity);
-  * a value check that needs no oracle: the single-pass 16-bit engines against the PRECISE engine on the same weights and inputs.  The
-    precise engine is pinned to < 1e-3 absolute against the reference's golden vectors at 64-128 px (tests/test_gpu_precise.py), so the
-    distance between the two modes bounds the 16-bit modes' full-size error: asserted at the same per-mode bounds as test_gpu_adm.py;
+  * the single-pass 16-bit engines against the PRECISE engine on the same weights and inputs, all chains of the batch.  The precise engine
+    is pinned to < 1e-3 absolute against the reference's golden vectors at 64-128 px (tests/test_gpu_precise.py) and at 256-512 px
+    (tests/test_gpu_fullsize_reference.py), so the distance between the two modes bounds the 16-bit modes' full-size error: asserted at the
+    same per-mode bounds as test_gpu_adm.py;
   * C3: the guidance gradient of a shard equals its slice of the full-batch gradient.
 """
 import pytest

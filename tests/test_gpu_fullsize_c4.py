@@ -1,6 +1,7 @@
 """GPU: BASELINE.json configs[3] at its full per-GPU size (StableDiffusion v1 latent UNet, 512x512 = 64x64 latents, batch 4 with
-classifier-free guidance = UNet batch 8, 77-token context, f16) through size-independent properties -- the CPU oracle cannot run this
-size in test time (value parity of the same engine against the oracle: the full 860 M UNet at 32x32 latents, tests/test_gpu_sd.py):
+classifier-free guidance = UNet batch 8, 77-token context, f16) through size-independent properties (value parity of the same engine: against the oracle
+with the full 860 M UNet at 32x32 latents in tests/test_gpu_sd.py, and against the reference's vendored ldm UNetModel at this very size,
+64x64 latents at UNet batch 8, in tests/test_gpu_fullsize_reference.py):
 
   * determinism: the same inputs twice give bit-identical predicted noise and latents;
   * chain independence (the basis of the replica sharding): permuting the batch permutes the outputs bit-exactly, and a rank holding

@@ -190,8 +190,9 @@ def test_adm_pixelart_64_mixed_vs_reference_golden():
 
 def test_full_size_512_mixed_vs_precise_engine_deterministic_and_chain_independent():
     """BASELINE configs[4]'s own size (512x512): every level of the shipped net on the weights-direct mixed kernels (128-channel tiles at full
-    resolution, two-source 768 -> 256, the 32x32 maps, the plain-f16 levels below and both level boundaries).  The CPU oracle cannot run this
-    size in test time: the reference here is the precise engine (3e-6 from the reference's golden at 128x128), absolute bound 1e-3; plus what
+    resolution, two-source 768 -> 256, the 32x32 maps, the plain-f16 levels below and both level boundaries).  The reference
+    here is the precise engine (3e-6 from the reference's golden at 128x128; both modes against the reference's own 512x512 output at batch 8:
+    test_gpu_fullsize_reference.py), absolute bound 1e-3; plus what
     must hold at any size: determinism and batch-permutation invariance, bit-exact."""
     from perceptor_amd.engine import ops
     from perceptor_amd.utils.synth import seeded_noise
