@@ -31,7 +31,13 @@ int pmi_abi_version(void);
  * (optionally nearest-2x upsampled) input with zero padding.  taps 9: dy, dx in -1..1
  * (3x3); taps 16 (stride 2 only, Hin = 2H, Win = 2W): dy = tap/4 - 1, dx = tap%4 - 1 in
  * -1..2, the 4x4 window of the input gradient of nearest-x2 + conv3x3 (Upsample2D) with
- * phase-folded weights.  Channels [0,C0) come
+ * phase-folded weights.  taps 9 with stride 2 and up 2: the input gradient of Downsample2D
+ * (pad right / bottom by one, 3x3 stride-2 convolution; stable_diffusion.py:175-192 through
+ * vae.encode) by output phase: the input is the low-resolution gradient Hin x Win, H = 2 Hin,
+ * W = 2 Win, M = images * H * W; output pixel (2p+a, 2q+b) sums the taps ky = a, kx = b (mod 2)
+ * at input pixels (p - ty, q - tx), ty < 2 - a, tx < 2 - b, and B holds the transposed taps
+ * phase-major (k offsets 0, 4, 6, 8 taps for the phases 2a + b = 0..3).  One source, no
+ * residual / per-sample bias / statistics / split-K / batch in that form.  Channels [0,C0) come
  * from A0, [C0,C0+C1) from A1 (skip-concat without materialising torch.cat).
  * Replaces: nn.Conv2d 3x3 / 1x1 / Conv1d k=1 / nn.Linear / einsum-bmm in
  *   guided_diffusion/unet.py:232-252 (ResBlock), :294-300 (AttentionBlock qkv/proj),
@@ -55,7 +61,7 @@ typedef struct {
   int32_t H, W, Hin, Win; /* conv mode only */
   int32_t taps;        /* 1, 9 or 16 */
   int32_t stride;      /* 1 or 2 */
-  int32_t up;          /* nearest x2 upsample of the input (Hin = H/2) */
+  int32_t up;          /* 1: nearest x2 upsample of the input (Hin = H/2); 2 (taps 9, stride 2): the phased Downsample2D adjoint */
   int32_t res_up;      /* residual is an [H/2 x W/2] grid read at (y>>1, x>>1): nearest x2 upsample of the skip path */
   int32_t act;         /* PMI_ACT_* */
   int32_t out_f32, res_f32;

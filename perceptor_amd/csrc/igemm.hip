@@ -14,6 +14,12 @@
 // the loads of k-tile t+1 are issued before the MFMAs of tile t and written after them.
 // Conv taps: 9 = 3x3 (dy, dx in -1..1); 16 = the 4x4 stride-2 window (dy, dx in -1..2) of the
 // Upsample2D adjoint, whose weights are the 3x3 kernel folded per output phase (engine/sd.py).
+// PHASED (taps 9, stride 2, up 2): the adjoint of Downsample2D (pad right / bottom by one, 3x3 stride-2 convolution).  The input is the
+// low-resolution gradient [Hin x Win], the output the 2Hin x 2Win one.  Output pixel (2p + a, 2q + b) only meets the kernel taps with
+// ky = a, kx = b (mod 2): 4 / 2 / 2 / 1 of them for the phases (0,0) (0,1) (1,0) (1,1), at the input pixels (p - ty, q - tx), ty, tx in
+// {0, 1}.  blockIdx.y is the phase (the 4-tap one first): the tap set is workgroup-uniform, a phase is a GEMM of M / 4 rows over its own
+// K range of the phase-packed weights (engine/sd.py: pack_downsample_adjoint_weights), and the epilogue scatters a row to its pixel.
+// 9 tap-products per 2 x 2 output block instead of the 36 of a 3x3 pass over a zero-inserted gradient.
 #include <cstdio>
 #include <cstdlib>
 #include "common.h"
@@ -28,8 +34,9 @@ constexpr int STAGE_BYTES = 2 * TILE_BYTES;  // activations + weights
 
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
-template <typename T, bool CONV, bool KFAST>
+template <typename T, bool CONV, bool KFAST, bool PHASED = false>
 __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
+  static_assert(!PHASED || CONV, "the phased geometry is a convolution");
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_BYTES];
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -40,11 +47,18 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
 #define GSTAMP(k) do {} while (0)
 #endif
   GSTAMP(0);
-  const int tiles_n = (a.N + BN - 1) / BN, tiles_m = (a.M + BM - 1) / BM;
+  // PHASED: rows, k range and tap grid of this workgroup's phase (otherwise the whole problem)
+  const int ph = PHASED ? (int)blockIdx.y : 0, pa = ph >> 1, pb = ph & 1;
+  const int ntx = 2 - pb;                                                     // taps along x: kx in {0, 2} or {1}
+  const int Mr = PHASED ? a.M >> 2 : a.M;
+  const int Kr = PHASED ? (2 - pa) * ntx * (a.C0 + a.C1) : a.K;
+  const int kofs = PHASED ? (ph == 0 ? 0 : 2 + 2 * ph) * (a.C0 + a.C1) : 0;    // first k of the phase: 0, 4, 6, 8 taps in
+  const bool up1 = !PHASED && a.up;
+  const int tiles_n = (a.N + BN - 1) / BN, tiles_m = (Mr + BM - 1) / BM;
   const int logical = xcd_remap(blockIdx.x, tiles_m * tiles_n);
   // Each XCD (own L2) gets a contiguous range of tiles.  Row-major ranges re-read all of B per XCD, column-major ranges all
   // of A: walk along the shorter operand so the longer one is split across the XCDs (ViT GEMMs: M = 2056, N up to 4096).
-  const bool nmajor = a.M < a.N;
+  const bool nmajor = Mr < a.N;
   const int m0 = (nmajor ? logical % tiles_m : logical / tiles_n) * BM, n0 = (nmajor ? logical / tiles_m : logical % tiles_n) * BN;
 
   const u16* A0 = (const u16*)a.A0;
@@ -62,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
   // ---- per-thread staging coordinates: 4 rows x one 16-byte chunk of each operand tile ----
   const int srow = tid >> 3, sc = tid & 7;
   const int Cin = a.C0 + a.C1;
-  const int Hv = a.up ? a.Hin * 2 : a.Hin, Wv = a.up ? a.Win * 2 : a.Win;
+  const int Hv = up1 ? a.Hin * 2 : a.Hin, Wv = up1 ? a.Win * 2 : a.Win;
   int ys[4], xs[4], nb[4];
   int64_t arow[4];
   int64_t brow[4];
@@ -70,7 +84,12 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
   for (int i = 0; i < 4; ++i) {
     const int m = m0 + srow + 32 * i;
     if (CONV) {
-      if (m < a.M) {
+      if (PHASED && m < Mr) {                 // rows of a phase run over the low-resolution grid
+        const int hw = a.Hin * a.Win;
+        const int img = m / hw, rem = m - img * hw;
+        const int y = rem / a.Win;
+        ys[i] = y; xs[i] = rem - y * a.Win; nb[i] = img * a.Hin;
+      } else if (m < Mr) {
         const int hw = a.H * a.W;
         const int img = m / hw, rem = m - img * hw;
         const int y = rem / a.W, x = rem - y * a.W;
@@ -79,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
         ys[i] = -(1 << 20); xs[i] = 0; nb[i] = 0;
       }
     } else {
-      arow[i] = m < a.M ? (int64_t)m : -1;
+      arow[i] = m < Mr ? (int64_t)m : -1;
     }
     const int n = n0 + srow + 32 * i;
     brow[i] = n < a.N ? (int64_t)n * a.ldb : -1;
@@ -91,10 +110,10 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
   // KFAST tiles are read with raw buffer loads (out-of-range offset = zero fill): no divergent branch around a load, so
   // the compiler keeps exact vmcnt counts and the two-tile lookahead survives (see conv3x3.hip).  Bases are moved to the
   // tile's first row / image so 32-bit offsets suffice.
-  const int hw_out = CONV ? a.H * a.W : 1;
+  const int hw_out = PHASED ? a.Hin * a.Win : CONV ? a.H * a.W : 1;
   const int img0 = CONV ? m0 / hw_out : 0;
   const int64_t a_skip = CONV ? (int64_t)img0 * a.Hin * a.Win : (int64_t)m0;            // rows (pixels) in front of the base
-  const int64_t a_rows = (CONV ? (int64_t)(a.M / hw_out) * a.Hin * a.Win : (int64_t)a.M) - a_skip;
+  const int64_t a_rows = (CONV ? (int64_t)(Mr / hw_out) * a.Hin * a.Win : (int64_t)a.M) - a_skip;
   const u16* const A0b = A0 + a_skip * a.lda0;
   const u16* const A1b = A1 ? A1 + a_skip * a.lda1 : A0b;
   const int64_t bytesA0 = ((a_rows - 1) * a.lda0 + a.C0) * 2, bytesA1 = A1 ? ((a_rows - 1) * a.lda1 + a.C1) * 2 : 0;
@@ -116,7 +135,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
       const uint32_t ld2 = (uint32_t)(second ? a.lda1 : a.lda0) * 2u;
       const uint32_t so = (uint32_t)(cbase - (second ? a.C0 : 0)) * 2u;
       int dy = 0, dx = 0;
-      if (CONV && a.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
+      if (PHASED) { dy = -(tap >> (ntx - 1)); dx = -(tap & (ntx - 1)); }
+      else if (CONV && a.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
       if (CONV && a.taps == 16) { dy = (tap >> 2) - 1; dx = (tap & 3) - 1; }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -124,25 +144,26 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
         if (CONV) {
           int iy = ys[i] + dy, ix = xs[i] + dx;
           const bool ok = iy >= 0 && iy < Hv && ix >= 0 && ix < Wv;
-          if (a.up) { iy >>= 1; ix >>= 1; }
+          if (up1) { iy >>= 1; ix >>= 1; }
           vo = ok && !dead ? (uint32_t)((nb[i] - img0 * a.Hin + iy) * a.Win + ix) * ld2 + (uint32_t)sc * 16u : PMI_BUF_OOB;
         } else {
           vo = dead ? PMI_BUF_OOB : (uint32_t)(srow + 32 * i) * ld2 + (uint32_t)sc * 16u;   // rows past M fall outside the resource
         }
         ra[i] = buf_load16(rs, vo, so);
-        rb[i] = buf_load16(rsrc_b, dead ? PMI_BUF_OOB : vob[i], (uint32_t)kt * (BK * 2));
+        rb[i] = buf_load16(rsrc_b, dead ? PMI_BUF_OOB : vob[i], (uint32_t)(kt * BK + kofs) * 2u);
       }
       return;
     }
     const int k = kt * BK + sc * 8;
-    const bool kok = k < a.K && !dead;
+    const bool kok = k < Kr && !dead;
     const int tap = k / Cin, ci = k - tap * Cin;
     const bool second = ci >= a.C0;
     const u16* base = second ? A1 : A0;
     const int ld = second ? a.lda1 : a.lda0;
     const int cc = second ? ci - a.C0 : ci;
     int dy = 0, dx = 0;
-    if (CONV && a.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
+    if (PHASED) { dy = -(tap >> (ntx - 1)); dx = -(tap & (ntx - 1)); }
+    else if (CONV && a.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
     if (CONV && a.taps == 16) { dy = (tap >> 2) - 1; dx = (tap & 3) - 1; }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -150,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
       if (CONV) {
         int iy = ys[i] + dy, ix = xs[i] + dx;
         if (kok && iy >= 0 && iy < Hv && ix >= 0 && ix < Wv) {
-          if (a.up) { iy >>= 1; ix >>= 1; }
+          if (up1) { iy >>= 1; ix >>= 1; }
           v = *(const uint4*)(base + ((int64_t)(nb[i] + iy) * a.Win + ix) * ld + cc);
         }
       } else {
@@ -158,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
       }
       ra[i] = v;
       uint4 w = make_uint4(0, 0, 0, 0);
-      if (kok && brow[i] >= 0) w = *(const uint4*)(Bw + brow[i] + k);
+      if (kok && brow[i] >= 0) w = *(const uint4*)(Bw + brow[i] + k + kofs);
       rb[i] = w;
     }
   };
@@ -181,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  const int nk_all = (a.K + BK - 1) / BK;
+  const int nk_all = (Kr + BK - 1) / BK;
   const int l31 = lane & 31, lhi = lane >> 5;
   // split-K (grid.z when batch <= 1): this workgroup reduces k-tiles [kt0, kt0 + nk) into its own fp32 slab
   int kt0 = 0, nk = nk_all;
@@ -253,6 +274,18 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
     return;
   }
   // ---- epilogue: lane = pixel (col), registers = 4 consecutive output channels x 4 groups ----
+  // row of D that GEMM row m lands in.  PHASED: pixel (2p + pa, 2q + pb) of the high-resolution grid (no residual, per-sample bias or
+  // statistics there: pmi_igemm rejects them, so every other use of m below is an unphased one)
+  auto orow = [&](int m) -> int64_t {
+    if constexpr (PHASED) {
+      const int hw = a.Hin * a.Win;
+      const int img = m / hw, rem = m - img * hw;
+      const int p = rem / a.Win, q = rem - p * a.Win;
+      return (int64_t)(img * a.H + 2 * p + pa) * a.W + 2 * q + pb;
+    } else {
+      return (int64_t)m;
+    }
+  };
   float* const stat = (float*)smem;            // [2 wave rows][BN][2] per-channel (sum, sumsq) of this tile (main loop is done with LDS)
   // Fast path (16-bit output, 16-byte aligned rows): each wave transposes its 64 x 64 tile through LDS and writes
   // 16 bytes per lane, 8 rows x 128 B per instruction, reading a 16-bit residual the same way.  In the accumulator layout a
@@ -319,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
           for (int e = 0; e < 8; ++e) { cs[e] += f[e]; cs[8 + e] += f[e] * f[e]; }
         }
       }
-      if (nok && m < a.M) *(uint4*)((u16*)a.D + offD + (int64_t)m * a.ldd + n0 + cl0) = v;
+      if (nok && m < Mr) *(uint4*)((u16*)a.D + offD + orow(m) * a.ldd + n0 + cl0) = v;
     }
     if (a.stats) {   // butterfly over the 8 lanes that share r8 (lane bits 3..5), halving the live values per step; one slot per wave row
       float b8[8], b4[4], b2[2];
@@ -396,7 +429,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int m = mrow[i];
-      if (m >= a.M) continue;
+      if (m >= Mr) continue;
+      const int64_t mo = orow(m);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int n = n0 + wc * 64 + j * 32 + 4 * lhi + 8 * g;
@@ -428,7 +462,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const pmi_igemm_args a) {
           *(uint2*)((u16*)a.D + o) = hi;
           *(uint2*)((u16*)a.D + o + a.split_out) = pack4<T>(l0, l1, l2, l3);
         } else {
-        const int64_t o = offD + (int64_t)m * a.ldd + n;
+        const int64_t o = offD + mo * a.ldd + n;
         if (a.out_f32) *(float4*)((float*)a.D + o) = make_float4(v[0], v[1], v[2], v[3]);
         else *(uint2*)((u16*)a.D + o) = pack4<T>(v[0], v[1], v[2], v[3]);
         }
@@ -512,12 +546,16 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const pmi_igemm_args
 
 template <typename T>
 int launch(const pmi_igemm_args& a, hipStream_t s) {
-  const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  const dim3 grid(tiles, 1, a.batch > 1 ? a.batch : (a.splitk > 1 ? a.splitk : 1)), block(256);
+  const bool phased = a.up == 2;          // Downsample2D adjoint: one grid slice of M / 4 rows per output phase
+  const int tiles = (((phased ? a.M / 4 : a.M) + BM - 1) / BM) * ((a.N + BN - 1) / BN);
+  const dim3 grid(tiles, phased ? 4 : 1, a.batch > 1 ? a.batch : (a.splitk > 1 ? a.splitk : 1)), block(256);
   const bool conv = a.taps != 1 || a.up || a.stride == 2;
   const int Cin = a.C0 + a.C1;
   const bool kfast = (Cin % BK == 0) && (a.C0 % BK == 0);
-  if (conv) {
+  if (phased) {
+    if (kfast) hipLaunchKernelGGL((igemm_kernel<T, true, true, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((igemm_kernel<T, true, false, true>), grid, block, 0, s, a);
+  } else if (conv) {
     if (kfast) hipLaunchKernelGGL((igemm_kernel<T, true, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((igemm_kernel<T, true, false>), grid, block, 0, s, a);
   } else {
@@ -553,7 +591,7 @@ static int g_wd_max_split = 8;      // A/B switch: pmi_set_option(11, n)
 // launch far fewer workgroups than the 256 CUs.  The caller then provides ws = S * M * N floats.
 int pmi_conv3x3_wd_splitk(const pmi_igemm_args* a, int cfg);        // conv_wd.hip
 extern "C" int pmi_igemm_splitk(const pmi_igemm_args* a) {
-  if (a->batch > 1 || (a->N & 3)) return 1;
+  if (a->batch > 1 || (a->N & 3) || a->up == 2) return 1;
   if (g_allow_halo) {
     const int halo = pmi_conv3x3_halo_config(a);
     if (halo >= 0) return pmi_conv3x3_wd_splitk(a, halo);
@@ -585,7 +623,7 @@ extern "C" int pmi_igemm_splitk(const pmi_igemm_args* a) {
 int pmi_igemm_halo_allowed(void) { return g_allow_halo; }
 
 extern "C" int pmi_igemm_stats_rows(const pmi_igemm_args* a) {
-  if (a->batch > 1 || a->splitk > 1) return 0;
+  if (a->batch > 1 || a->splitk > 1 || a->up == 2) return 0;
   const int halo = g_allow_halo ? pmi_conv3x3_halo_config(a) : -1;
   if (a->split_out) return halo >= 6 ? (a->H / 8) * (a->W / 32) : 0;    // split outputs: the weights-direct conv3x3 epilogue only (the generic kernel takes none)
   if (halo == 3) return 0;                                             // few-output-channel config: no statistics epilogue
@@ -634,6 +672,10 @@ extern "C" int pmi_igemm(const pmi_igemm_args* a, pmi_stream_t stream) {
   // taps 16: the 4x4 stride-2 window of the Upsample2D adjoint (rows / columns 2y-1 .. 2y+2 of the high-resolution gradient)
   if (a->taps == 16 && (a->stride != 2 || a->up || a->res_up || a->Hin != 2 * a->H || a->Win != 2 * a->W)) return bad_arg(__LINE__);
   if (a->stride != 1 && a->stride != 2) return bad_arg(__LINE__);
+  // up 2: the Downsample2D adjoint by output phase (taps 9 on phase-packed weights, stride 2 = the forward's): one source, M = images x 2Hin x 2Win,
+  // and nothing in the epilogue that is indexed by the GEMM row (residual, per-sample bias, statistics, split outputs); no split-K, no batch
+  if (a->up == 2 && (a->taps != 9 || a->stride != 2 || a->res_up || a->A1 || a->C1 || a->R || a->nbias || a->stats || a->splitk > 1 || a->batch > 1 ||
+                     a->split_out || a->split_in || a->pro_a || a->D2 || a->aux || a->dtype == PMI_DT_F16X2 || (a->M & 3))) return bad_arg(__LINE__);
   if (a->K != a->taps * (a->C0 + a->C1)) return bad_arg(__LINE__);
   if (a->R && (a->ldr & 3)) return bad_arg(__LINE__);
   // (split_out: the group width ops.split_group gives a tensor of N channels -- 32, or N itself for 8 / 16 / 24; the epilogues write 4-channel

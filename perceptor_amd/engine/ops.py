@@ -502,6 +502,36 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
     return out
 
 
+def downsample_adjoint_args(g: torch.Tensor, lin: PackedLinear, out: torch.Tensor) -> IgemmArgs:
+    """pmi_igemm's phased geometry (taps 9, stride 2, up 2) for g [N, h, w, C] -> out [N, 2h, 2w, C']: H x W is the output grid, Hin x Win the
+    gradient's, M counts output pixels (a quarter of them per phase)."""
+    n, h, w, c = g.shape
+    a = IgemmArgs()
+    a.A0, a.B, a.D = ptr(g), ptr(lin.w), ptr(out)
+    a.M, a.N, a.K = 4 * n * h * w, lin.n_p, lin.K
+    a.C0, a.lda0, a.ldb, a.ldd = c, g.stride(-2), lin.K, out.stride(-2)
+    a.H, a.W, a.Hin, a.Win, a.hw = 2 * h, 2 * w, h, w, 4 * h * w
+    a.taps, a.stride, a.up = 9, 2, 2
+    a.out_f32 = int(out.dtype == torch.float32)
+    a.alpha = 1.0
+    a.batch, a.batch_inner = 1, 1
+    a.dtype = lin.dt
+    return a
+
+
+def downsample_adjoint(g: torch.Tensor, lin: PackedLinear, *, out_f32: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Input gradient of Downsample2D (pad right / bottom by one, 3x3 stride-2 convolution without padding) in one launch: g [N, h, w, C]
+    is the gradient wrt its output, `lin` the phase-packed weights (engine/sd.py: pack_downsample_adjoint_weights), the result
+    [N, 2h, 2w, C'] the gradient wrt its input.  Every output phase gathers only the taps that reach it -- no zero-inserted
+    [N, 2h, 2w, C] buffer and a quarter of the MFMA work of a 3x3 pass over one."""
+    n, h, w, c = g.shape
+    assert lin.taps == 9 and not lin.split and c == lin.cin_p, (lin.taps, c, lin.cin_p)
+    if out is None:
+        out = _empty((n, 2 * h, 2 * w, lin.n_p), torch.float32 if out_f32 else _hip.TORCH_DTYPE[lin.dt], g.device)
+    call("pmi_igemm", C.byref(downsample_adjoint_args(g, lin, out)))
+    return out
+
+
 def geglu_linear(x: torch.Tensor, lin: PackedLinear) -> torch.Tensor:
     """x [M, K] @ lin (columns packed as 16 value | 16 gate per 32: interleave_geglu) -> value * gelu(gate) [M, N / 2].
     In the GEMM's epilogue where the weights-direct kernel takes the shape; otherwise the GEMM followed by the gate pass."""

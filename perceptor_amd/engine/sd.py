@@ -184,6 +184,29 @@ def fold_upsample_weights(weight: torch.Tensor) -> torch.Tensor:
     return folded.permute(1, 0, 2, 3).contiguous()
 
 
+# phase-major tap order of the Downsample2D adjoint: output phase (a, b) = (row, column) parity meets the kernel taps ky = a, kx = b (mod 2)
+DOWN_ADJOINT_TAPS = ((0, 0), (0, 2), (2, 0), (2, 2),      # phase (0, 0): gradient pixels (p, q), (p, q-1), (p-1, q), (p-1, q-1)
+                     (0, 1), (2, 1),                      # phase (0, 1): (p, q), (p-1, q)
+                     (1, 0), (1, 2),                      # phase (1, 0): (p, q), (p, q-1)
+                     (1, 1))                              # phase (1, 1): (p, q)
+
+
+def pack_downsample_adjoint_weights(weight: torch.Tensor) -> torch.Tensor:
+    """Weights of the one-pass adjoint of Downsample2D (pad right / bottom by one, then a 3x3 stride-2 convolution without padding).
+
+    With y[oy, ox] = sum over ky, kx of W[ky, kx] x[2 oy + ky, 2 ox + kx], input pixel (2p + a, 2q + b) is read by tap (ky, kx) of output
+    (p + (a - ky) / 2, q + (b - kx) / 2) only where ky = a and kx = b (mod 2):
+        dx[2p + a, 2q + b] = sum over ty < 2 - a, tx < 2 - b of W[a + 2 ty, b + 2 tx]^T dy[p - ty, q - tx]
+    (dy outside its grid dropped): 4, 2, 2 and 1 taps for the four phases, 9 per 2x2 block of dx instead of the 36 of a 3x3 pass over a
+    zero-inserted dy.  No flip and no sum: the taps are only transposed and reordered phase-major (DOWN_ADJOINT_TAPS), which is the K
+    order pmi_igemm's phased geometry reads.  weight [Cout, Cin, 3, 3] -> [Cin, Cout, 3, 3] float64 whose flattened last two axes are
+    that order."""
+    w = weight.detach().double()
+    ky = [t[0] for t in DOWN_ADJOINT_TAPS]
+    kx = [t[1] for t in DOWN_ADJOINT_TAPS]
+    return w[:, :, ky, kx].permute(1, 0, 2).reshape(w.shape[1], w.shape[0], 3, 3).contiguous()
+
+
 def unet_state_dict_shapes(cfg: SdConfig) -> Dict[str, Tuple[int, ...]]:
     sh, ted = _Shapes(), 4 * cfg.block_out[0]
     sh.lin("time_embedding.linear_1", ted, cfg.block_out[0]); sh.lin("time_embedding.linear_2", ted, ted)
@@ -310,6 +333,60 @@ class _Blocks:
         o = ops.igemm(at.view(m, cc), w[a + ".proj"], residual=h.view(m, cc), want_stats=True, hw=h2 * w2)
         return ops.view_nhwc(o, n, h2, w2)
 
+
+    # ---- what the VAE decoder's and encoder's input gradients share: the tape-keeping forms of the ResnetBlock2D and the mid attention, and
+    # their backward steps (see VaeDecoderEngine) ----------------------------------------------------------------------------------------
+    def _vae_resnet_train(self, k, x, tape, groups, eps):
+        dt, w = self.dt, self.w
+        ca, cb, p1 = ops.group_norm_coeffs_train(x, *w[k + ".gn1"], groups, dt, eps=eps)
+        h = ops.igemm(x, w[k + ".conv1"], prologue=(ca, cb, ACT_SILU), want_stats=True)
+        ca2, cb2, p2 = ops.group_norm_coeffs_train(h, *w[k + ".gn2"], groups, dt, eps=eps)
+        skip = ops.igemm(x, w[k + ".skip"]) if (k + ".skip") in w else x
+        tape.append(("res", k, x, (ca, cb, p1), h, (ca2, cb2, p2)))
+        return ops.igemm(h, w[k + ".conv2"], residual=skip, prologue=(ca2, cb2, ACT_SILU), want_stats=True)
+
+    def _vae_attention_train(self, a, x, tape, groups):
+        dt, w = self.dt, self.w
+        n, h2, w2, cc = x.shape
+        m = n * h2 * w2
+        ca, cb, parts = ops.group_norm_coeffs_train(x, *w[a + ".gn"], groups, dt, eps=1e-6)
+        hn = torch.empty_like(x)
+        call("pmi_gn_apply", ptr(x), None, cc, ptr(ca), ptr(cb), None, ptr(hn), n, h2, w2, cc, ACT_NONE, 0, dt)
+        qkv = ops.igemm(hn.view(m, cc), w[a + ".qkv"])
+        at, pm = ops.attention_train(qkv.view(n, h2 * w2, 3 * cc), 1, dt)       # = ops.attention's batched-GEMM path (head dim > 160)
+        o = ops.igemm(at.view(m, cc), w[a + ".proj"], residual=x.view(m, cc), want_stats=True, hw=h2 * w2)
+        tape.append(("attn", a, x, (ca, cb, parts), qkv, pm))
+        return ops.view_nhwc(o, n, h2, w2)
+
+    def _vae_res_back(self, rec, g, sd, groups, eps):
+        _, k, x, gn1, h, gn2 = rec
+        dt, w, dev = self.dt, self.w, self.device
+        d_a2 = ops.igemm(g, ops.packed_dx(w, k + ".conv2T", sd[k + ".conv2.weight"], dt, dev))                  # wrt SiLU(GN2(h))
+        dh, _ = ops.group_norm_backward(h, d_a2, *gn2, w[k + ".gn2"][0], groups, dt, act=ACT_SILU, eps=eps)
+        d_a1 = ops.igemm(dh, ops.packed_dx(w, k + ".conv1T", sd[k + ".conv1.weight"], dt, dev))                 # wrt SiLU(GN1(x))
+        gs = ops.igemm(g, ops.packed_dx(w, k + ".skipT", sd[k + ".conv_shortcut.weight"], dt, dev)) if (k + ".skip") in w else g
+        gx, _ = ops.group_norm_backward(x, d_a1, *gn1, w[k + ".gn1"][0], groups, dt, act=ACT_SILU, gadd0=gs, eps=eps)
+        return gx
+
+    def _vae_attn_back(self, rec, g, sd, groups):
+        _, a, x, gn, qkv, pm = rec
+        dt, w, dev = self.dt, self.w, self.device
+        n, h2, w2, cc = x.shape
+        t, m = h2 * w2, n * h2 * w2
+        da = ops.igemm(g.view(m, cc), ops.packed_dx(w, a + ".projT", sd[a + ".proj_attn.weight"], dt, dev))
+        dqkv = ops.attention_backward(qkv.view(n, t, 3 * cc), pm, da.view(n, t, cc), 1, dt)
+        if a + ".qkvT" not in w:
+            ops.packed_dx(w, a + ".qkvT", torch.cat([sd[f"{a}.{nm}.weight"].cpu() for nm in ("query", "key", "value")], 0), dt, dev)
+        dhn = ops.igemm(dqkv.view(m, 3 * cc), w[a + ".qkvT"]).view(n, h2, w2, cc)
+        gx, _ = ops.group_norm_backward(x, dhn, *gn, w[a + ".gn"][0], groups, dt, act=ACT_NONE, gadd0=g, eps=1e-6)
+        return gx
+
+    def _down_back(self, k, g, sd):
+        """Gradient wrt the input of Downsample2D from g = gradient wrt its output [N, h, w, C]: one phased pmi_igemm launch writes the
+        [N, 2h, 2w, C] result (ops.downsample_adjoint)."""
+        if k + ".phase" not in self.w:
+            self.w[k + ".phase"] = PackedLinear(pack_downsample_adjoint_weights(sd[k + ".weight"].cpu()).float(), None, self.dt, self.device)
+        return ops.downsample_adjoint(g, self.w[k + ".phase"])
 
 class SdUnetEngine(_Blocks):
     def __init__(self, cfg: SdConfig, state_dict: Dict[str, torch.Tensor], device, dtype="f16"):
@@ -762,28 +839,6 @@ class VaeDecoderEngine(_Blocks):
     # backward() walks the tape once.  A convolution's dX is pmi_igemm on transposed, flipped weights; GroupNorm + SiLU backward is
     # pmi_gn_bwd_*; the attention's is ops.attention_backward on the kept P; an up-sampler's adjoint is one stride-2 4x4-tap pmi_igemm on
     # phase-folded weights (fold_upsample_weights) instead of dX at the high resolution + pmi_upsample_nearest2_bwd.
-    def _resnet_train(self, k, x, tape, groups, eps):
-        dt, w = self.dt, self.w
-        ca, cb, p1 = ops.group_norm_coeffs_train(x, *w[k + ".gn1"], groups, dt, eps=eps)
-        h = ops.igemm(x, w[k + ".conv1"], prologue=(ca, cb, ACT_SILU), want_stats=True)
-        ca2, cb2, p2 = ops.group_norm_coeffs_train(h, *w[k + ".gn2"], groups, dt, eps=eps)
-        skip = ops.igemm(x, w[k + ".skip"]) if (k + ".skip") in w else x
-        tape.append(("res", k, x, (ca, cb, p1), h, (ca2, cb2, p2)))
-        return ops.igemm(h, w[k + ".conv2"], residual=skip, prologue=(ca2, cb2, ACT_SILU), want_stats=True)
-
-    def _attention_train(self, a, x, tape, groups):
-        dt, w = self.dt, self.w
-        n, h2, w2, cc = x.shape
-        m = n * h2 * w2
-        ca, cb, parts = ops.group_norm_coeffs_train(x, *w[a + ".gn"], groups, dt, eps=1e-6)
-        hn = torch.empty_like(x)
-        call("pmi_gn_apply", ptr(x), None, cc, ptr(ca), ptr(cb), None, ptr(hn), n, h2, w2, cc, ACT_NONE, 0, dt)
-        qkv = ops.igemm(hn.view(m, cc), w[a + ".qkv"])
-        at, pm = ops.attention_train(qkv.view(n, h2 * w2, 3 * cc), 1, dt)       # = ops.attention's batched-GEMM path (head dim > 160)
-        o = ops.igemm(at.view(m, cc), w[a + ".proj"], residual=x.view(m, cc), want_stats=True, hw=h2 * w2)
-        tape.append(("attn", a, x, (ca, cb, parts), qkv, pm))
-        return ops.view_nhwc(o, n, h2, w2)
-
     @torch.no_grad()
     def forward_train(self, latents: torch.Tensor, scale: float = 1.0 / 0.18215, to_images: bool = True):
         """As forward(), keeping what backward() needs: (images NCHW fp32, tape).  For head dims above 160 (SD-v1: 512) the value equals
@@ -792,12 +847,12 @@ class VaeDecoderEngine(_Blocks):
         h = self._conv_in(latents, scale)
         g, eps = cfg.groups, 1e-6
         rec: List[tuple] = []
-        h = self._resnet_train("decoder.mid_block.resnets.0", h, rec, g, eps)
-        h = self._attention_train("decoder.mid_block.attentions.0", h, rec, g)
-        h = self._resnet_train("decoder.mid_block.resnets.1", h, rec, g, eps)
+        h = self._vae_resnet_train("decoder.mid_block.resnets.0", h, rec, g, eps)
+        h = self._vae_attention_train("decoder.mid_block.attentions.0", h, rec, g)
+        h = self._vae_resnet_train("decoder.mid_block.resnets.1", h, rec, g, eps)
         for kind, k in self.plan:
             if kind == "res":
-                h = self._resnet_train(k, h, rec, g, eps)
+                h = self._vae_resnet_train(k, h, rec, g, eps)
             else:
                 rec.append(("up", k))
                 h = ops.igemm(h, w[k], up=True, want_stats=True)
@@ -806,29 +861,6 @@ class VaeDecoderEngine(_Blocks):
         tape = {"rec": rec, "last": (h, (ca, cb, parts)), "scale": float(scale), "to_images": bool(to_images),
                 "in_shape": tuple(latents.shape), "out_shape": tuple(out.shape)}
         return out, tape
-
-    def _res_back(self, rec, g, sd, groups, eps):
-        _, k, x, gn1, h, gn2 = rec
-        dt, w, dev = self.dt, self.w, self.device
-        d_a2 = ops.igemm(g, ops.packed_dx(w, k + ".conv2T", sd[k + ".conv2.weight"], dt, dev))                  # wrt SiLU(GN2(h))
-        dh, _ = ops.group_norm_backward(h, d_a2, *gn2, w[k + ".gn2"][0], groups, dt, act=ACT_SILU, eps=eps)
-        d_a1 = ops.igemm(dh, ops.packed_dx(w, k + ".conv1T", sd[k + ".conv1.weight"], dt, dev))                 # wrt SiLU(GN1(x))
-        gs = ops.igemm(g, ops.packed_dx(w, k + ".skipT", sd[k + ".conv_shortcut.weight"], dt, dev)) if (k + ".skip") in w else g
-        gx, _ = ops.group_norm_backward(x, d_a1, *gn1, w[k + ".gn1"][0], groups, dt, act=ACT_SILU, gadd0=gs, eps=eps)
-        return gx
-
-    def _attn_back(self, rec, g, sd, groups):
-        _, a, x, gn, qkv, pm = rec
-        dt, w, dev = self.dt, self.w, self.device
-        n, h2, w2, cc = x.shape
-        t, m = h2 * w2, n * h2 * w2
-        da = ops.igemm(g.view(m, cc), ops.packed_dx(w, a + ".projT", sd[a + ".proj_attn.weight"], dt, dev))
-        dqkv = ops.attention_backward(qkv.view(n, t, 3 * cc), pm, da.view(n, t, cc), 1, dt)
-        if a + ".qkvT" not in w:
-            ops.packed_dx(w, a + ".qkvT", torch.cat([sd[f"{a}.{nm}.weight"].cpu() for nm in ("query", "key", "value")], 0), dt, dev)
-        dhn = ops.igemm(dqkv.view(m, 3 * cc), w[a + ".qkvT"]).view(n, h2, w2, cc)
-        gx, _ = ops.group_norm_backward(x, dhn, *gn, w[a + ".gn"][0], groups, dt, act=ACT_NONE, gadd0=g, eps=1e-6)
-        return gx
 
     @torch.no_grad()
     def backward(self, tape, d_out: torch.Tensor, state_dict) -> torch.Tensor:
@@ -849,9 +881,9 @@ class VaeDecoderEngine(_Blocks):
         g, _ = ops.group_norm_backward(h, d_act, *gn, self.gn_out[0], g_, dt, act=ACT_SILU, eps=eps)
         for rec in reversed(tape["rec"]):
             if rec[0] == "res":
-                g = self._res_back(rec, g, sd, g_, eps)
+                g = self._vae_res_back(rec, g, sd, g_, eps)
             elif rec[0] == "attn":
-                g = self._attn_back(rec, g, sd, g_)
+                g = self._vae_attn_back(rec, g, sd, g_)
             else:
                 g = self._up_back(rec[1], g, sd)
         lp = self.pq.cin_p
@@ -893,10 +925,9 @@ class VaeEncoderEngine(_Blocks):
         xp[:, 1:hh + 1, 1:ww + 1] = h
         return ops.igemm(xp, lin, stride=2)[:, 1:, 1:].contiguous()
 
-    @torch.no_grad()
-    def forward(self, images: torch.Tensor):
-        """images NCHW fp32 in [0, 1] -> (mean, logvar) NCHW fp32 [N, latent, H/8, W/8] of the latent distribution."""
-        cfg, dt, dev, w = self.cfg, self.dt, self.device, self.w
+    def _conv_in(self, images):
+        """images NCHW fp32 in [0, 1] -> 2*img - 1 as NHWC 16-bit (3 channels padded to 8) -> conv_in (with its GroupNorm statistics)."""
+        cfg, dt, dev = self.cfg, self.dt, self.device
         if not images.is_cuda:
             raise RuntimeError("VaeEncoderEngine runs on a HIP device only (no CPU fallback)")
         images = images.float().contiguous()
@@ -906,7 +937,25 @@ class VaeEncoderEngine(_Blocks):
             raise ValueError(f"images must be [N, {cfg.out_channels}, H, W] with H, W divisible by {down}")
         x = torch.empty((n, hh, ww, 8), dtype=_hip.TORCH_DTYPE[dt], device=dev)
         call("pmi_nchw_to_nhwc", ptr(images), ptr(x), n, c, hh, ww, 8, 2.0, -1.0, dt)      # diffusion_space.encode: 2*img - 1
-        h = ops.igemm(x, self.conv_in, want_stats=True)
+        return ops.igemm(x, self.conv_in, want_stats=True)
+
+    def _output(self, h, ca, cb):
+        """conv_out on SiLU(GroupNorm(h)) given the norm's coefficients -> quant_conv -> (mean, logvar) NCHW fp32."""
+        dev = self.device
+        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))        # [n, h/8, w/8, 8] fp32
+        n, ho, wo, c2 = y.shape
+        m = n * ho * wo
+        mom = ops.linear_f32(y.view(m, c2), self.quant[0], self.quant[1])                  # quant_conv (1x1, 8 -> 8) in exact fp32
+        out = torch.empty((n, c2, ho, wo), dtype=torch.float32, device=dev)
+        call("pmi_nhwc_to_nchw", ptr(mom), c2, ptr(out), n, ho, wo, c2, 1.0, 0.0)
+        lc = self.cfg.latent_channels
+        return out[:, :lc].contiguous(), out[:, lc:2 * lc].contiguous()
+
+    @torch.no_grad()
+    def forward(self, images: torch.Tensor):
+        """images NCHW fp32 in [0, 1] -> (mean, logvar) NCHW fp32 [N, latent, H/8, W/8] of the latent distribution."""
+        cfg, dt, w = self.cfg, self.dt, self.w
+        h = self._conv_in(images)
         g, eps = cfg.groups, 1e-6
         for kind, k in self.plan:
             h = self._resnet(k, h, None, None, g, eps) if kind == "res" else self._down(h, w[k])
@@ -914,11 +963,90 @@ class VaeEncoderEngine(_Blocks):
         h = self._vae_attention("encoder.mid_block.attentions.0", h, g)
         h = self._resnet("encoder.mid_block.resnets.1", h, None, None, g, eps)
         ca, cb = ops.group_norm_coeffs(h, *self.gn_out, g, dt, eps=eps)
-        y = ops.igemm(h, self.conv_out, out_f32=True, prologue=(ca, cb, ACT_SILU))        # [n, h/8, w/8, 8] fp32
-        _, ho, wo, c2 = y.shape
-        m = n * ho * wo
-        mom = ops.linear_f32(y.view(m, c2), self.quant[0], self.quant[1])                  # quant_conv (1x1, 8 -> 8) in exact fp32
-        out = torch.empty((n, c2, ho, wo), dtype=torch.float32, device=dev)
-        call("pmi_nhwc_to_nchw", ptr(mom), c2, ptr(out), n, ho, wo, c2, 1.0, 0.0)
-        lc = cfg.latent_channels
-        return out[:, :lc].contiguous(), out[:, lc:2 * lc].contiguous()
+        return self._output(h, ca, cb)
+
+    # ---- input gradient (d loss / d images through the frozen encoder: pixel-space optimisation against SD) ---------------------------
+    # The decoder's scheme (VaeDecoderEngine) in the other direction.  forward_train() issues forward()'s launch sequence and keeps, per
+    # ResnetBlock2D, x, the GN1 coefficients and partials, h and the GN2 ones; for the mid attention its input, GN, q|k|v and P; the last h
+    # with its GN.  Down-samplers and convolutions are linear: nothing is kept.  backward() walks the tape once: quant_conv^T, conv_out^T,
+    # GroupNorm + SiLU backward, the mid block, the plan in reverse (_vae_res_back; a down-sampler's adjoint is ONE phased pmi_igemm launch,
+    # _down_back), conv_in^T with fp32 output, NCHW.
+    @torch.no_grad()
+    def forward_train(self, images: torch.Tensor):
+        """As forward(), keeping what backward() needs: ((mean, logvar), tape).  For head dims above 160 (SD-v1: 512) the values equal
+        forward()'s bit for bit; a 64-channel mid attention runs forward()'s d64 kernel there and the batched GEMMs here (rounding-level)."""
+        cfg, dt, w = self.cfg, self.dt, self.w
+        h = self._conv_in(images)
+        g, eps = cfg.groups, 1e-6
+        rec: List[tuple] = []
+        for kind, k in self.plan:
+            if kind == "res":
+                h = self._vae_resnet_train(k, h, rec, g, eps)
+            else:
+                rec.append(("down", k))
+                h = self._down(h, w[k])
+        h = self._vae_resnet_train("encoder.mid_block.resnets.0", h, rec, g, eps)
+        h = self._vae_attention_train("encoder.mid_block.attentions.0", h, rec, g)
+        h = self._vae_resnet_train("encoder.mid_block.resnets.1", h, rec, g, eps)
+        ca, cb, parts = ops.group_norm_coeffs_train(h, *self.gn_out, g, dt, eps=eps)
+        mean, logvar = self._output(h, ca, cb)
+        tape = {"rec": rec, "last": (h, (ca, cb, parts)), "in_shape": tuple(images.shape), "out_shape": tuple(mean.shape)}
+        return (mean, logvar), tape
+
+    def _quant_back(self, sd, both: bool) -> PackedLinear:
+        """quant_conv^T (1x1, 8 -> 8) over the cotangent as it arrives: d_mean and d_logvar are separate 4-channel tensors, each laid out as
+        an 8-channel NHWC tensor (channels 4..7 zero), read through the two source pointers of one pmi_igemm launch -- K = 16 with the
+        rows of quant_conv's weight for (mean | 0 | logvar | 0); `both` False: d_logvar = 0, K = 8."""
+        key = "quant_convT2" if both else "quant_convT1"
+        if key not in self.w:
+            lc = self.cfg.latent_channels
+            wq = sd["quant_conv.weight"].detach().cpu().double().flatten(1)                  # [2 lc (moments), 2 lc (conv_out channels)]
+            wt = torch.zeros((2 * lc, 16 if both else 8), dtype=torch.float64)
+            wt[:, :lc] = wq[:lc].t()
+            if both:
+                wt[:, 8:8 + lc] = wq[lc:].t()
+            self.w[key] = PackedLinear(wt.float(), None, self.dt, self.device)
+        return self.w[key]
+
+    @torch.no_grad()
+    def backward(self, tape, d_mean: torch.Tensor, d_logvar: Optional[torch.Tensor], state_dict) -> torch.Tensor:
+        """d loss / d images (NCHW fp32, the images' shape, including the factor 2 of 2*img - 1) from d loss / d mean and d loss / d logvar
+        (NCHW fp32, the shape of forward_train()'s moments; d_logvar None = zero) and its tape.  `state_dict`: the VAE's tensors by name
+        (StableDiffusion.vae.state_dict()); the transposed and phase-packed weights are packed from it on the first call and kept on the
+        engine.  f16 engines scale the cotangent by ONE power of two over both tensors on the way in and back on the way out (the rule of
+        ops.grad_to_nhwc); bf16 needs no scaling."""
+        cfg, dt, dev, w = self.cfg, self.dt, self.device, self.w
+        parts = [d_mean] if d_logvar is None else [d_mean, d_logvar]
+        for d in parts:
+            if not d.is_cuda:
+                raise RuntimeError("VaeEncoderEngine runs on a HIP device only (no CPU fallback)")
+            if tuple(d.shape) != tape["out_shape"]:
+                raise ValueError(f"d_mean / d_logvar must have the moments' shape {tape['out_shape']}, got {tuple(d.shape)}")
+        sd = state_dict
+        g_, eps = cfg.groups, 1e-6
+        parts = [d.float().contiguous() for d in parts]
+        n, lc, ho, wo = parts[0].shape
+        gscale = 1.0
+        if dt == _hip.DT_F16:
+            amax = torch.empty((len(parts), n), dtype=torch.float32, device=dev)
+            for i, d in enumerate(parts):
+                call("pmi_quantile_abs", ptr(d), ptr(amax[i]), n, lc * ho * wo, 1.0)
+            gscale = ops.f16_grad_scale(amax.flatten().tolist())
+        gs = []
+        for d in parts:
+            gq = torch.empty((n, ho, wo, 8), dtype=_hip.TORCH_DTYPE[dt], device=dev)
+            call("pmi_nchw_to_nhwc", ptr(d), ptr(gq), n, lc, ho, wo, 8, gscale, 0.0, dt)
+            gs.append(gq)
+        g = ops.igemm(gs[0].view(-1, 8), self._quant_back(sd, len(gs) == 2), a1=gs[1].view(-1, 8) if len(gs) == 2 else None).view(n, ho, wo, 8)
+        h, gn = tape["last"]
+        d_act = ops.igemm(g, ops.packed_dx(w, "encoder.conv_outT", sd["encoder.conv_out.weight"], dt, dev))
+        g, _ = ops.group_norm_backward(h, d_act, *gn, self.gn_out[0], g_, dt, act=ACT_SILU, eps=eps)
+        for rec in reversed(tape["rec"]):
+            if rec[0] == "res":
+                g = self._vae_res_back(rec, g, sd, g_, eps)
+            elif rec[0] == "attn":
+                g = self._vae_attn_back(rec, g, sd, g_)
+            else:
+                g = self._down_back(rec[1], g, sd)
+        gx = ops.igemm(g, ops.packed_dx(w, "encoder.conv_inT", sd["encoder.conv_in.weight"], dt, dev), out_f32=True)      # [n, H, W, 4] fp32
+        return ops.grad_to_nchw(gx, cfg.out_channels, 2.0 / gscale)

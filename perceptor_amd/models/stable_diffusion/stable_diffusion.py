@@ -58,6 +58,49 @@ class _Decode(torch.autograd.Function):
         return g, None
 
 
+class _Encode(torch.autograd.Function):
+    """encode(images) with an input gradient, as autograd provides upstream through vae.encode (stable_diffusion.py:175-192): forward and
+    backward are the HIP encoder's forward_train / backward (engine/sd.py).  With z = 0.18215 (mean + eps std), std = exp(logvar_c / 2)
+    and logvar_c = clamp(logvar, -30, 20): d_mean = 0.18215 g, and for "sample" d_logvar = 0.18215 g eps std / 2 where the clamp is
+    inactive, 0 where it is active ("mode": d_logvar = 0).  The noise is the one the forward drew.  The VAE is frozen."""
+
+    @staticmethod
+    def forward(ctx, images, method, model):
+        eng = model._engine("encoder")
+        (mean, logvar), tape = eng.forward_train(images)
+        ctx.model, ctx.engine, ctx.tape, ctx.noise_std = model, eng, tape, None
+        if method == "sample":
+            std = torch.exp(0.5 * logvar.clamp(-30.0, 20.0))
+            noise_std = sampler.randn_like(mean) * std
+            ctx.noise_std = noise_std * ((logvar > -30.0) & (logvar < 20.0))
+            return sampler.lincomb2(mean, 0.18215, noise_std, 0.18215)
+        return sampler.lincomb2(mean, 0.18215)
+
+    @staticmethod
+    def backward(ctx, grad_latents):
+        g = grad_latents.float().contiguous()
+        d_mean = sampler.lincomb2(g, 0.18215)
+        d_logvar = None if ctx.noise_std is None else sampler.lincomb2(g * ctx.noise_std, 0.18215 * 0.5)
+        gx = ctx.engine.backward(ctx.tape, d_mean, d_logvar, ctx.model.vae.state_dict())
+        ctx.tape = None
+        return gx, None, None
+
+
+class _Diffuse(torch.autograd.Function):
+    """diffuse_latents with the gradient to the denoised latents (alpha per sample), as autograd provides upstream through
+    ``denoised * alpha + noise * sigma`` (stable_diffusion.py:377-382): what lets a loss on the UNet's prediction of a diffused encoding reach
+    ``encode``'s images.  The value is the no-grad path's sampler.lincomb2 launch; the noise and the schedule get no gradient."""
+
+    @staticmethod
+    def forward(ctx, latents, alphas, noise, sigmas):
+        ctx.alphas = alphas
+        return sampler.lincomb2(latents, alphas, noise, sigmas)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return sampler.lincomb2(grad.float().contiguous(), ctx.alphas), None, None, None
+
+
 class _PredictedNoise(torch.autograd.Function):
     """predicted_noise(x, encodings) with input gradients, as autograd provides upstream through the UNet call under autocast
     (stable_diffusion.py:259-271): forward and backward are the HIP UNet's forward_train / backward (engine/sd.py).  The UNet is frozen and
@@ -96,6 +139,19 @@ class StableDiffusion(torch.nn.Module):
         diffused_latents = pred.guided(dl.grad).step(to_index)
 
     Otherwise ``decode`` runs the no-grad decoder (no tape, same bits).
+
+    ``encode`` / ``latents`` are differentiable with respect to the images in the same way (grad mode on and the images require grad), for
+    both methods ("sample" keeps the noise it drew), so pixels or an image parameterisation can be optimised against SD -- score
+    distillation, img2img with a pixel-space optimiser, a loss on the latents of a drawn image::
+
+        x = images.requires_grad_()
+        z = sd.latents(x)
+        loss = ((sd.predicted_noise(sd.diffuse_latents(z, index, noise), index, conditioning) - noise) ** 2).mean()
+        loss.backward()
+        x.grad
+
+    Without ``requires_grad`` (or under ``torch.no_grad()``) the no-grad encoder runs: no tape, same bits.  ``diffuse_latents`` passes the
+    gradient on to latents that require grad (times alpha); its noise and the schedule get none.
 
     ``predicted_noise`` / ``predictions`` / ``predictions_pair`` are differentiable in the diffused latents in the same way (grad mode on and
     the latents require grad): ``pred.predicted_noise`` and ``pred.denoised_latents`` then carry the UNet's input gradient, e.g. for
@@ -219,7 +275,10 @@ class StableDiffusion(torch.nn.Module):
             raise Exception(f"Height must be divisible by 32, got {h}")
         if w % 32 != 0:
             raise Exception(f"Width must be divisible by 32, got {w}")
-        mean, logvar = self._engine("encoder").forward(images.to(self.device))
+        images = images.to(self.device)
+        if torch.is_grad_enabled() and images.requires_grad and method in ("sample", "mode"):
+            return _Encode.apply(images, method, self)
+        mean, logvar = self._engine("encoder").forward(images)
         if method == "sample":
             std = torch.exp(0.5 * logvar.clamp(-30.0, 20.0))
             return sampler.lincomb2(mean, 0.18215, sampler.randn_like(mean) * std, 0.18215)
@@ -378,7 +437,10 @@ class StableDiffusion(torch.nn.Module):
         indices = self.indices(indices)
         if noise is None:
             noise = sampler.randn_like(denoised_latents)
-        return sampler.lincomb2(denoised_latents, self.schedule_alphas[indices], noise, self.schedule_sigmas[indices])
+        alphas, sigmas = self.schedule_alphas[indices], self.schedule_sigmas[indices]
+        if torch.is_grad_enabled() and denoised_latents.requires_grad:
+            return _Diffuse.apply(denoised_latents.to(self.device), alphas, noise, sigmas)
+        return sampler.lincomb2(denoised_latents, alphas, noise, sigmas)
 
     @torch.no_grad()
     def sample(self, text: str, from_index: int = 999, to_index: int = 0, n_steps: int = 50, guidance_scale: float = 7.0,
