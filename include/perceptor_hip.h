@@ -92,14 +92,17 @@ typedef struct {
   void* D2;            /* optional second output [M][ldd] 16-bit: the PRE-activation value (c_fc output kept for the backward pass) */
   const void* aux;     /* optional [M][ldd] 16-bit: the output is multiplied by act'(aux) with act = aux_act (dh * gelu'(h_pre) of the c_proj input gradient) */
   int32_t aux_act;
-  int32_t reserved3;
+  int32_t reserved3;   /* 1: split-K weights-direct GEMM, the caller consumes the raw slabs; 2: Bf holds no phase weights -- an up-sampling conv3x3 stays off tile config 9 */
 } pmi_igemm_args;
 int pmi_igemm(const pmi_igemm_args* a, pmi_stream_t stream);
 /* >= 0 when an LDS-halo conv3x3 kernel takes this shape.  csrc/conv3x3.hip: tile config 0: 8x32 px x 256 ch, 1: 16x32 x 128, 2: 8x32 x 128 with two
  * workgroups per CU, 3: 8x32 px x <= 32 output channels (also a split input with fp32 output, N <= 32: a plain K over the 2 Cin physical
  * channels); csrc/conv_wd.hip (weights-direct, needs Bf != NULL): 4: 8x32 px x 256 ch (32x32x16 MFMA), 6: 8x32 px x 256 ch (16x16x32 MFMA,
  * 64-channel chunks), 7: 8x32 px x 128 ch (16x16x32, 32-channel chunks, also a masked Cout tail), 8: at most 32 input channels, one source,
- * the whole K in registers.  Split (precise / mixed) outputs take configs 6 / 7 / 8 only.  -1 when pmi_igemm uses the generic implicit-GEMM
+ * the whole K in registers; csrc/conv_up_wd.hip: 9: up = 1 by output phase -- four 2x2 convolutions on the low-resolution grid, 8x32 low-resolution
+ * positions x one phase x 256 ch, Bf = [N/32][phase 2a + b][Cin/64][2 dx][2][2 dy][2][64 lanes][8] with the tap sums a = 0: w0 | w1 + w2, a = 1: w0 + w1 | w2
+ * per axis (one source, no residual / output activation, N % 256 == 0, Win % 32 == 0, Hin % 8 == 0; the MFMA work issued is 4/9 of the algorithmic
+ * 9-tap FLOP).  Split (precise / mixed) outputs take configs 6 / 7 / 8 only.  -1 when pmi_igemm uses the generic implicit-GEMM
  * kernel (which has no fused prologue). */
 int pmi_conv3x3_halo_config(const pmi_igemm_args* a);
 /* 1 when the weights-direct GEMM (csrc/gemm_wd.hip) takes this call: plain GEMM (taps 1, one source, no per-sample bias / statistics / prologue),
@@ -110,14 +113,15 @@ int pmi_igemm_splitk(const pmi_igemm_args* a);
 /* number of per-image partial rows the fused output statistics of this call would produce (0: not available for this shape) */
 int pmi_igemm_stats_rows(const pmi_igemm_args* a);
 /* debugging / A-B switches: key 0 = allow the LDS-halo conv3x3 kernel (default 1, returns the previous value);
- * key 1 = force halo tile config 0/1/2 where eligible (-1 = automatic);
+ * key 1 = force a conv3x3 tile config where eligible (-1 = automatic; 6 / 7 keep up-sampling convolutions on the gather route, 9 puts them on the phased one);
  * key 2 = prefer the 8-wave 256-channel halo config over two 4-wave workgroups per CU where the grid allows (default 1);
  * key 6 = allow the weights-direct conv3x3 kernel (default 1); key 7 = its 16x16x32-MFMA form, tile config 6, instead of config 4 (default 1);
  * key 8 = allow its 128-channel form, tile config 7 (4 waves, two workgroups per CU), for Cout % 256 != 0 (default 1);
  * key 13 = allow its first-convolution form, tile config 8 (at most 32 input channels, the whole K in registers) (default 1);
  * key 9 = query-tile rows per wave of pmi_attn_flash (0 = automatic); key 10 = allow split-K in the weights-direct conv3x3 (default 1);
  * key 11 = largest split-K factor of the weights-direct GEMM (default 8); key 12 = workgroup count below which that GEMM uses its
- * 128-column tiles (default 128); key 14 = most query chunks per key tile of pmi_attn_flash_bwd_kv (0 = automatic, 1 = the unsplit key role).
+ * 128-column tiles (default 128); key 14 = most query chunks per key tile of pmi_attn_flash_bwd_kv (0 = automatic, 1 = the unsplit key role);
+ * key 15 = allow tile config 9, up-sampling conv3x3 by output phase (default 1; 0: the gather route of configs 6 / 7 takes them).
  * `python bench.py --opt "k=v,..."` sets them for a same-box A/B.
  * The library links no vendor GEMM / BLAS: every kernel it launches is in csrc/. */
 int pmi_set_option(int key, int value);

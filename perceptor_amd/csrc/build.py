@@ -8,12 +8,12 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libperceptor_hip.so")
-SOURCES = ["igemm.hip", "conv3x3.hip", "conv_wd.hip", "gemm_wd.hip", "norm.hip", "attn.hip", "attn_flash.hip", "elementwise.hip", "clip.hip", "f32gemm.hip", "sampling.hip", "backward.hip", "resnet.hip"]
+SOURCES = ["igemm.hip", "conv3x3.hip", "conv_wd.hip", "conv_up_wd.hip", "gemm_wd.hip", "norm.hip", "attn.hip", "attn_flash.hip", "elementwise.hip", "clip.hip", "f32gemm.hip", "sampling.hip", "backward.hip", "resnet.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # per-file additions.  conv_wd.hip: no SLP vectorisation -- the vectoriser packs the patch staging's f32 arithmetic into v_pk_fma_f32 /
 # v_pk_mul_f32, which cost MORE vector-issue time beside MFMAs than the two scalar ops they replace (MI355X_MICROARCH.md, per-instruction
 # constants) and need ~800 v_mov to pair registers: 128 -> 128 @512x512 0.715 -> 0.694 ms, c5 bf16 42.39 -> 42.13 ms (same-box A/B)
-FILE_FLAGS = {"conv_wd.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {"conv_wd.hip": ["-fno-slp-vectorize"], "conv_up_wd.hip": ["-fno-slp-vectorize"]}
 
 
 def _stale(out: str, deps) -> bool:

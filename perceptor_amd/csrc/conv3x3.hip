@@ -423,11 +423,14 @@ void pmi_conv3x3_wd_mf16(int v) { g_wd_mf16 = v; }
 void pmi_conv3x3_wd128(int v) { g_wd128 = v; }
 static int g_wd_smallc = 1;    // pmi_set_option(13, v): allow config 8 (at most 32 input channels)
 void pmi_conv3x3_wd_smallc(int v) { g_wd_smallc = v; }
+static int g_up_phase = 1;     // pmi_set_option(15, v): allow config 9 (up-sampling convolutions by output phase, conv_up_wd.hip)
+void pmi_conv3x3_up_phase(int v) { g_up_phase = v; }
 void pmi_conv3x3_force_config(int cfg) { g_force_cfg = cfg; }
 void pmi_conv3x3_prefer_256(int v) { g_prefer0 = v; }
 
 // Returns the tile config the halo kernel runs for this shape (0: 8x32 px x 256 ch / 8 waves, 1: 16x32 x 128 / 8 waves,
-// 2: 8x32 x 128 / 4 waves x 2 workgroups per CU, 3: 8x32 px x <= 32 channels) or -1 if the shape needs the generic kernel.
+// 2: 8x32 x 128 / 4 waves x 2 workgroups per CU, 3: 8x32 px x <= 32 channels; 4, 6, 7, 8: conv_wd.hip; 9: conv_up_wd.hip) or -1 if the
+// shape needs the generic kernel.
 extern "C" int pmi_conv3x3_halo_config(const pmi_igemm_args* a) {
   if (a->taps != 9 || a->stride != 1 || a->batch > 1) return -1;
   const int Cin = a->C0 + a->C1;
@@ -469,6 +472,13 @@ extern "C" int pmi_conv3x3_halo_config(const pmi_igemm_args* a) {
     if (g_force_cfg == 7) return ok7t ? 7 : -1;
     return (g_force_cfg < 0 && g_wd128 && ok7t && t8 * ((a->N + 127) / 128) >= 256) ? 7 : -1;
   }
+  // config 9: nearest-x2 input by output phase (conv_up_wd.hip): four 2x2 convolutions on the low-resolution grid, 4/9 of the gather route's
+  // MFMAs.  One source, no residual, no output activation, 256-channel tiles; Bf is then the PHASE packing (reserved3 = 2: the caller has
+  // none, the gather route keeps the call).  The workgroup count (phases included) is the gather route's, so is config 6's threshold.
+  if (a->Bf && g_wd && g_wd_mf16 && g_up_phase && a->up == 1 && !a->A1 && a->C1 == 0 && !a->R && !a->split_in && !a->split_out && a->act == PMI_ACT_NONE &&
+      a->reserved3 != 2 && (a->N % 256) == 0 && (a->Win % 32) == 0 && (a->Hin % 8) == 0 && (!a->pro_a || a->C0 <= 2048) &&
+      (g_force_cfg == 9 || (g_force_cfg < 0 && (long)(a->M / (a->H * a->W)) * (a->Hin / 8) * (a->Win / 32) * 4 * (a->N / 256) >= 192)))
+    return 9;
   if (a->Bf && g_wd && (!a->pro_a || a->C0 + a->C1 <= 2048)) {   // weights-direct kernel (its prologue coefficient table holds 2048 channels): 4 / 6 = 256-channel tiles (64-channel chunks), 7 = 128-channel tiles (32-channel chunks)
     const int t8 = a->M / (a->H * a->W) * (a->H / 8) * (a->W / 32);
     const bool ok4 = (a->N % 256) == 0;

@@ -577,6 +577,7 @@ int launch(const pmi_igemm_args& a, hipStream_t s) {
 extern "C" int pmi_conv3x3_halo_config(const pmi_igemm_args* a);
 int pmi_conv3x3_halo_launch(const pmi_igemm_args* a, int cfg, void* stream);
 int pmi_conv3x3_wd_launch(const pmi_igemm_args* a, int cfg, void* stream);   // conv_wd.hip: tile configs 4, 6
+int pmi_conv3x3_up_wd_launch(const pmi_igemm_args* a, void* stream);          // conv_up_wd.hip: tile config 9
 extern "C" int pmi_gemm_wd_eligible(const pmi_igemm_args* a);                 // gemm_wd.hip: plain GEMMs with fragment-ordered weights
 int pmi_gemm_wd_tile_rows(const pmi_igemm_args* a, int splitk);
 int pmi_gemm_wd_launch(const pmi_igemm_args* a, void* stream);
@@ -637,6 +638,7 @@ void pmi_attn_flash_kv_chunks(int v);
 void pmi_conv3x3_wd_splitk_enable(int v);   // conv_wd.hip
 void pmi_gemm_wd_few_wgs(int v);            // gemm_wd.hip
 void pmi_conv3x3_wd_smallc(int v);          // conv3x3.hip
+void pmi_conv3x3_up_phase(int v);
 
 extern "C" int pmi_set_option(int key, int value) {
   if (key == 0) { const int old = g_allow_halo; g_allow_halo = value; return old; }
@@ -651,6 +653,7 @@ extern "C" int pmi_set_option(int key, int value) {
   if (key == 12) { pmi_gemm_wd_few_wgs(value); return 0; }
   if (key == 13) { pmi_conv3x3_wd_smallc(value); return 0; }
   if (key == 14) { pmi_attn_flash_kv_chunks(value); return 0; }
+  if (key == 15) { pmi_conv3x3_up_phase(value); return 0; }
   return PMI_ERR_ARG;
 }
 
@@ -709,6 +712,7 @@ extern "C" int pmi_igemm(const pmi_igemm_args* a, pmi_stream_t stream) {
     PMI_CHECK_LAUNCH();
     return PMI_OK;
   }
+  if (halo == 9) return pmi_conv3x3_up_wd_launch(a, stream);
   if (halo >= 4) {
     const int rc = pmi_conv3x3_wd_launch(a, halo, stream);
     if (rc != PMI_OK || a->splitk <= 1) return rc;

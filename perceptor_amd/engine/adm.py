@@ -186,7 +186,7 @@ class AdmEngine:
                 elif isinstance(l, _Res):
                     p = l.p
                     self.w[p + ".gn1"] = (f32(p + ".in_layers.0.weight"), f32(p + ".in_layers.0.bias"))
-                    self.w[p + ".conv1"] = lin(p + ".in_layers.2", sources=l.srcs)
+                    self.w[p + ".conv1"] = lin(p + ".in_layers.2", sources=l.srcs, up_phase=l.up)       # (an up block's conv1 reads nearest-x2(x): phase weights)
                     self.w[p + ".gn2"] = (f32(p + ".out_layers.0.weight"), f32(p + ".out_layers.0.bias"))
                     self.w[p + ".conv2"] = lin(p + ".out_layers.3")
                     if l.cin != l.cout:
@@ -200,7 +200,7 @@ class AdmEngine:
                     self.w[p + ".qkv"] = lin(p + ".qkv")
                     self.w[p + ".proj"] = lin(p + ".proj_out")
                 elif isinstance(l, _Resample) and cfg.conv_resample:
-                    self.w[l.p] = lin(l.p + (".conv" if l.up else ".op"))
+                    self.w[l.p] = lin(l.p + (".conv" if l.up else ".op"), up_phase=l.up)
         if self.precise:
             self.emb_all = (torch.cat(emb_w, 0).to(dev).contiguous(), torch.cat(emb_b, 0).to(dev).contiguous())
         else:

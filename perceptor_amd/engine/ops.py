@@ -62,10 +62,12 @@ class PackedLinear:
     the f16 weights are duplicated along K in the same pattern: W*hi + W*lo accumulates in fp32 on the MFMA.  `sources` gives the
     logical channel counts of a two-pointer concat input (each source is its own precise tensor with its own grouping).
     concat_sources = False keeps two-source fp32 weights a two-pointer layer (their low part rounded away, with a warning): the mixed
-    mode's fused-prologue configs read the two sources through their own pointers."""
+    mode's fused-prologue configs read the two sources through their own pointers.
+    up_phase = True: the layer convolves a nearest-x2 up-sampled input (ops.igemm(..., up=True)); where its shape can take the phased
+    kernel (csrc/conv_up_wd.hip) the phase weights are summed HERE, from the unrounded weights (frag16_up)."""
 
     def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor], dt: int, device, cin_pad: Optional[int] = None, sources=None,
-                 concat_sources: bool = True):
+                 concat_sources: bool = True, up_phase: bool = False):
         w = weight.detach().float()
         if w.ndim == 3:   # Conv1d k=1
             w = w[..., 0]
@@ -123,6 +125,32 @@ class PackedLinear:
             self.b = b.to(device)
         self.dt = dt
         self._frag = {}
+        if up_phase and not self.split and kh == 3 and kw == 3 and self.n_p % 256 == 0 and self.cin_p % 64 == 0:
+            self._frag[("up", 64)] = self._pack_up(packed.view(self.n_p, 3, 3, self.cin_p), 64, device, dt)
+
+    @staticmethod
+    def _pack_up(w: torch.Tensor, ck: int, device, dt: int) -> torch.Tensor:
+        """w: fp32 [N, dy, dx, Cin], unrounded -> the phase weights in the kernel's fragment order (see frag16_up)."""
+        n, _, _, cin = w.shape
+        # tap sums per axis: phase 0 reads (low-resolution index - 1 | index) with (w0 | w1 + w2), phase 1 (index | index + 1) with (w0 + w1 | w2)
+        rows = torch.stack([torch.stack([w[:, 0], w[:, 1] + w[:, 2]], 1), torch.stack([w[:, 0] + w[:, 1], w[:, 2]], 1)], 1)   # [N, a, u, dx, Cin]
+        eff = torch.stack([torch.stack([rows[:, :, :, 0], rows[:, :, :, 1] + rows[:, :, :, 2]], 3),
+                           torch.stack([rows[:, :, :, 0] + rows[:, :, :, 1], rows[:, :, :, 2]], 3)], 2)                       # [N, a, b, u, v, Cin]
+        eff = eff.to(device=device, dtype=_hip.TORCH_DTYPE[dt])                                                               # rounded once
+        e = eff.view(n // 32, 2, 16, 2, 2, 2, 2, cin // ck, ck // 32, 4, 8)      # nb, cb, r16, a, b, u (dy), v (dx), chunk, k32, q4, j
+        return e.permute(0, 3, 4, 7, 6, 8, 5, 1, 9, 2, 10).contiguous()
+
+    def frag16_up(self, ck: int) -> Optional[torch.Tensor]:
+        """Phase weights of a convolution over a nearest-x2 up-sampled input (csrc/conv_up_wd.hip, tile config 9): output parity (a, b) is a
+        2x2 convolution on the low-resolution grid whose taps are sums of the 3x3 ones, summed in fp32 from the weights the layer was
+        constructed with and rounded once: [N/32][phase 2a + b][Cin/ck][dx][ck/32][dy][16-channel block][lane = 16*(k quarter) + channel][8 k].
+        None unless the layer was constructed with up_phase=True (no fp32 copy of the weights is kept to build it later)."""
+        return self._frag.get(("up", ck))
+
+    def up_weights(self) -> torch.Tensor:
+        """The phase weights as packed, back in [N, a, b, u, v, Cin] order (tests: the kernel's own arithmetic)."""
+        f = self._frag[("up", 64)]                      # nb, a, b, chunk, v, k32, u, cb, q4, r16, j
+        return f.permute(0, 7, 9, 1, 2, 6, 4, 3, 5, 8, 10).reshape(self.n_p, 2, 2, 2, 2, self.cin_p)
 
     @property
     def K(self):
@@ -411,9 +439,11 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
     if conv and lin.taps == 9 and stride == 1 and HALO_ENABLED and WD_ENABLED and lin.n_p % 32 == 0 and ((lin.n_p >= 128 and lin.cin_p % 64 == 0) or (lin.cin_p <= 32 and a1 is None)):
         a.Bf = 1                       # ask which tile config the weights-direct kernel would run, then hand it that packing
         a.pro_a = 1 if (prologue is not None and not lin.split) else None     # (the table size limit depends on a fused prologue)
+        if up and lin.frag16_up(64) is None:
+            a.reserved3 = 2            # no phase weights: the up-sampling convolution stays on the gather route (config 9 needs them)
         cfg = _hip.lib().pmi_conv3x3_halo_config(C.byref(a))
         a.pro_a = None
-        a.Bf = ptr(lin.frag16(64)) if cfg == 6 else ptr(lin.frag16(32)) if cfg == 7 else ptr(lin.frag(64)) if cfg == 4 else ptr(lin.frag_c8()) if cfg == 8 else None
+        a.Bf = ptr(lin.frag16_up(64)) if cfg == 9 else ptr(lin.frag16(64)) if cfg == 6 else ptr(lin.frag16(32)) if cfg == 7 else ptr(lin.frag(64)) if cfg == 4 else ptr(lin.frag_c8()) if cfg == 8 else None
     if pre_out is not None or act_grad_of is not None:
         a.D2, a.aux, a.aux_act = ptr(pre_out), ptr(act_grad_of), act_grad
     # (split weights: their duplicated K is an ordinary K for the weights-direct GEMM; its epilogues write plain 16-bit or fp32 rows only)
