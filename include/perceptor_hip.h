@@ -262,13 +262,15 @@ int pmi_guided_update(const float* pred, const float* grad, const float* s_from,
                       float* out, int N, int64_t chw, pmi_stream_t s);
 
 /* remaining Predictions algebra (predictions.py:101-145,174-179 ; velocity_diffusion/predictions.py:107-200):
- * out = ca[n]*a + cb[n]*b + cc[n] with per-sample coefficients (b, cb, cc optional); clamp with per-sample bounds */
+ * out = ca[n]*a + cb[n]*b + cc[n] with per-sample coefficients (b, cb, cc optional); clamp with per-sample bounds, Tensor.clamp's
+ * values: a NaN input stays NaN */
 int pmi_lincomb2(const float* a, const float* b, const float* ca, const float* cb, const float* cc, float* out, int N,
                  int64_t chw, pmi_stream_t s);
 int pmi_clamp(const float* a, const float* lo, const float* hi, float* out, int N, int64_t chw, pmi_stream_t s);
 
 /* ---- Predictions variants and clamp_with_grad (csrc/sampling.hip), fp32, one row per sample ------------------
- * pmi_quantile_abs: out[n] = torch.quantile(|x[n, :]|, q) (linear interpolation), radix select -- replaces the quantile in
+ * pmi_quantile_abs: out[n] = torch.quantile(|x[n, :]|, q) (linear interpolation; equal order statistics are returned as they are, so q = 1 is
+ *   the row's max |x| also when that is inf), radix select -- replaces the quantile in
  *   Predictions.dynamic_threshold (guided_diffusion/predictions.py:156-172 ; velocity_diffusion/predictions.py:148-164).
  * pmi_randn: standard-normal noise for step(eta>0) / resample_noise / noisy_reverse_step (predictions.py:61-98,126-145), replacing
  *   torch.randn_like.  Philox4x32-10 + Box-Muller; element e of the draw (seed, stream) is a function of (seed, stream,
@@ -278,7 +280,7 @@ int pmi_clamp(const float* a, const float* lo, const float* hi, float* out, int 
  *   rows sorted ascending into work[rows][pmi_sort_rows_padded(n)] (bitonic network, +inf padding), then
  *   out[0] = mean |sorted - Normal(0,1).icdf(linspace(0.5/n, 1-0.5/n, n))|^power (power 1 or 2); partial = 1024 floats of workspace.
  * pmi_clamp_grad: backward of clamp_with_grad (transforms/clamp_with_grad.py:8-23) with per-sample bounds:
- *   out = grad * (grad * (x - clamp(x, lo, hi)) >= 0).                                                                          */
+ *   out = grad * (grad * (x - clamp(x, lo, hi)) >= 0), the mask multiplied as there: a NaN gradient stays NaN, a blocked infinite one is NaN. */
 int pmi_quantile_abs(const float* x, float* out, int N, int64_t n, float q, pmi_stream_t s);
 int pmi_randn(float* out, int64_t n, int64_t first_element, int64_t seed_bits, int64_t stream_bits, pmi_stream_t s);
 int pmi_philox4x32_10(uint32_t* out4, int64_t counter_lo, int64_t counter_hi, int64_t key, pmi_stream_t s);

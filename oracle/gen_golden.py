@@ -299,6 +299,22 @@ def gen_vdiff2():
         del m
 
 
+RESIZE2_CASES = (("40x100_64x48", (1, 3, 40, 100), (64, 48)), ("37x53_64x64", (1, 3, 37, 53), (64, 64)), ("4x5_9x11", (1, 3, 4, 5), (9, 11)),
+                 ("75x100_32x100", (1, 3, 75, 100), (32, 100)), ("64x64_63x65", (2, 3, 64, 64), (63, 65)))
+
+
+def gen_clip_resize2():
+    """FULL outputs of the reference's resize at the regimes clip_resize.npz (four shapes, every third pixel) leaves out: mixed direction,
+    inputs shorter than the kernel support, an axis with scale 1, a size change by one.  Part of gen_clip; `clip_resize2` alone writes
+    only this file."""
+    rz = R.ref("transforms.resize.resize_right")
+    out = {}
+    for tag, shape, target in RESIZE2_CASES:
+        img = seeded_noise(shape, 51) * 0.25 + 0.5
+        out["rz_" + tag] = rz.resize(img, out_shape=target).contiguous()
+    save("clip_resize2", **out)
+
+
 def gen_clip():
     rz = R.ref("transforms.resize.resize_right")
     ru = R.ref("models.ruclip.model")
@@ -308,6 +324,7 @@ def gen_clip():
         img = seeded_noise(shape, 51) * 0.25 + 0.5
         out["rz_" + tag] = rz.resize(img, out_shape=target)[:, :, ::3, ::3].contiguous()
     save("clip_resize", **out)
+    gen_clip_resize2()
     from oracle.clip_vit import CLIP_MEAN, CLIP_STD, VIT_CONFIGS
     for tag, size, n in (("tiny", 48, 2), ("tiny-odd", 40, 2), ("ViT-B-32", 256, 2)):
         res, patch, width, layers, heads, odim = VIT_CONFIGS[tag]

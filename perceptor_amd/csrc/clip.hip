@@ -550,7 +550,8 @@ extern "C" int pmi_patchify(const float* img, const float* mean, const float* st
   return PMI_OK;
 }
 extern "C" int pmi_unpatchify(const float* dcol, const float* stdv, float* dimg, int N, int R, int P, int Kp, float mul, pmi_stream_t s) {
-  if (!dcol || !stdv || !dimg || N <= 0 || R % P) return PMI_ERR_ARG;
+  // dcol is fp32: no Kp % 8 rule as in pmi_patchify, but every row must hold the 3 P^2 columns the kernel reads
+  if (!dcol || !stdv || !dimg || N <= 0 || R <= 0 || P <= 0 || R % P || Kp < (int64_t)3 * P * P) return PMI_ERR_ARG;
   hipLaunchKernelGGL(unpatchify_kernel, dim3(grid_for((int64_t)N * 3 * R * R)), dim3(256), 0, ST, dcol, stdv, dimg, N, R, P, Kp, mul);
   PMI_CHECK_LAUNCH();
   return PMI_OK;

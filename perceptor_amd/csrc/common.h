@@ -216,6 +216,10 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + idx;
 }
 
+// torch.clamp(x, lo, hi) on one value: min(max(x, lo), hi) that PROPAGATES a NaN input (fminf / fmaxf return the other operand, which would
+// paint a diverged sample with the valid value lo)
+__device__ __forceinline__ float clamp_keep_nan(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
+
 #define PMI_CHECK_LAUNCH()                                   \
   do {                                                       \
     hipError_t e__ = hipGetLastError();                      \

@@ -313,13 +313,13 @@ __global__ __launch_bounds__(256) void lincomb2_kernel(const float* __restrict__
   }
 }
 
-// clamp with per-sample bounds (static / dynamic thresholding forward)
+// clamp with per-sample bounds (static / dynamic thresholding forward); a NaN input stays NaN like Tensor.clamp
 __global__ __launch_bounds__(256) void clamp_kernel(const float* __restrict__ a, const float* lo, const float* hi,
                                                     float* __restrict__ out, int N, int64_t chw) {
   const int64_t total = (int64_t)N * chw;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int n = (int)(i / chw);
-    out[i] = fminf(fmaxf(a[i], lo[n]), hi[n]);
+    out[i] = clamp_keep_nan(a[i], lo[n], hi[n]);
   }
 }
 

@@ -84,8 +84,9 @@ __global__ __launch_bounds__(QT) void quantile_abs_kernel(const float* __restric
   }
   if (tid == 0) {
     const float a = __uint_as_float(prefix), b = __uint_as_float(best);
-    // at::lerp for floats: the two forms keep the result monotone and exact at w = 0 and w = 1
-    out[blockIdx.x] = w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.f - w);
+    // at::lerp for floats: the two forms keep the result monotone and exact at w = 0 and w = 1.  Equal order statistics are returned as they
+    // are: the lerp of inf with inf is inf + w * (inf - inf) = NaN, and q = 1 (the per-sample max |x| of the callers) must stay the amax
+    out[blockIdx.x] = best == prefix ? a : (w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.f - w));
   }
 }
 
@@ -260,9 +261,10 @@ __global__ __launch_bounds__(256) void clamp_grad_kernel(const float* __restrict
   if (i >= total) return;
   const int64_t nidx = i / chw;
   const float v = x[i], gi = g[i];
-  const float c = fminf(fmaxf(v, lo[nidx]), hi[nidx]);
-  // pass the gradient where the clamp is inactive, or where following it moves the value back towards the interval
-  out[i] = (gi * (v - c) >= 0.f) ? gi : 0.f;
+  const float c = clamp_keep_nan(v, lo[nidx], hi[nidx]);
+  // pass the gradient where the clamp is inactive, or where following it moves the value back towards the interval.  The mask MULTIPLIES
+  // as in grad * (grad * (x - clamp(x)) >= 0): a NaN gradient stays NaN and an infinite one blocked by the mask gives inf * 0 = NaN
+  out[i] = gi * ((gi * (v - c) >= 0.f) ? 1.f : 0.f);
 }
 
 }  // namespace
