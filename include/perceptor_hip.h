@@ -122,9 +122,31 @@ int pmi_igemm_stats_rows(const pmi_igemm_args* a);
  * key 11 = largest split-K factor of the weights-direct GEMM (default 8); key 12 = workgroup count below which that GEMM uses its
  * 128-column tiles (default 128); key 14 = most query chunks per key tile of pmi_attn_flash_bwd_kv (0 = automatic, 1 = the unsplit key role);
  * key 15 = allow tile config 9, up-sampling conv3x3 by output phase (default 1; 0: the gather route of configs 6 / 7 takes them).
+ * key 16 = allow the fused conv2 + skip launch, pmi_conv3x3_skip (default 1; 0: pmi_conv3x3_skip_eligible answers 0 and callers keep the skip GEMM).
  * `python bench.py --opt "k=v,..."` sets them for a same-box A/B.
  * The library links no vendor GEMM / BLAS: every kernel it launches is in csrc/. */
 int pmi_set_option(int key, int value);
+
+/* ---- ResBlock conv2 with the two-source 1x1 skip convolution folded into its K loop ----------------------------------------------
+ * D = conv3x3(silu(pro_a * h + pro_b)) + Wf * (X0 | X1) + bias: `a` describes the 3x3 convolution over h exactly as for pmi_igemm
+ * (fragment-ordered Bf, fused SiLU prologue, R = NULL, bias = conv2's bias + the skip convolution's, summed in fp32 by the caller); the
+ * skip product is accumulated in the same fp32 accumulators before the epilogue, so its own output tensor, its read-back as the residual
+ * and one rounding to 16 bits disappear; output statistics see conv + skip.  X0 [M][ld0], X1 [M][ld1] (or NULL, C1 = 0): the block's raw
+ * input on the OUTPUT grid H x W, C0 / C1 multiples of 64; Wf: the [N][C0 + C1] skip weights in fragment order
+ * [N/32][(C0 + C1)/32][16-channel block (2)][lane = 16*(k quarter) + channel][8 k].
+ * Replaces: guided_diffusion/unet.py:232-252 ResBlock `self.skip_connection(x) + h` with x = th.cat([h, hs.pop()], dim=1) of :650-652.
+ * pmi_conv3x3_skip_eligible: the tile config (6 or 7, non-zero) pmi_conv3x3_skip runs the call in -- the caller packs Bf for it (any non-NULL
+ * Bf for the query) -- or 0: f16 / bf16, SiLU prologue, alpha = 1, no output activation, no residual / res_up / up / split-K / split (mixed,
+ * precise) tensors / fp32 output, 16-byte aligned pointers; N % 256 == 0 takes the 256-channel tiles (config 6), any other N % 128 == 0 the
+ * 128-channel tiles (config 7), bf16 only.  Answer and config are functions of the layer and the map, never of the number of images: a fused
+ * launch is never split along K.  pmi_conv3x3_skip returns PMI_ERR_ARG where the query answers 0, without a launch. */
+typedef struct {
+  const void* X0; const void* X1; const void* Wf;
+  int32_t C0, C1;      /* channels of X0 / X1 */
+  int32_t ld0, ld1;    /* elements between consecutive pixels of X0 / X1 */
+} pmi_skip_args;
+int pmi_conv3x3_skip_eligible(const pmi_igemm_args* a, const pmi_skip_args* k);
+int pmi_conv3x3_skip(const pmi_igemm_args* a, const pmi_skip_args* k, pmi_stream_t stream);
 
 /* ---- "precise" mode helpers (dtype 2: hi + lo f16 pairs, eps max-abs error < 1e-3 vs the fp32 reference path) ----------------
  * exact-fp32 batched GEMM on the f32-input MFMA: D[b][m][n] = act(alpha * sum_k A[b][m][k] * B[b][n][k] + bias[n]); transB: B is [k][n]; transA: A is

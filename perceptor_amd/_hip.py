@@ -48,6 +48,12 @@ class IgemmArgs(C.Structure):
     ]
 
 
+class SkipArgs(C.Structure):
+    """pmi_skip_args: the raw two-source input of a ResBlock and its 1x1 skip weights in fragment order (pmi_conv3x3_skip)."""
+    _fields_ = [("X0", C.c_void_p), ("X1", C.c_void_p), ("Wf", C.c_void_p),
+                ("C0", C.c_int32), ("C1", C.c_int32), ("ld0", C.c_int32), ("ld1", C.c_int32)]
+
+
 class GemmF32Args(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("bias", C.c_void_p), ("D", C.c_void_p),
                 ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("lda", C.c_int32), ("ldb", C.c_int32), ("ldd", C.c_int32),
@@ -66,6 +72,8 @@ _PROTOS = {
     "pmi_igemm_splitk": ([C.POINTER(IgemmArgs)],),
     "pmi_set_option": ([_I, _I],),
     "pmi_gemm_wd_eligible": ([C.POINTER(IgemmArgs)],),
+    "pmi_conv3x3_skip_eligible": ([_P, _P],),      # (IgemmArgs, SkipArgs by reference)
+    "pmi_conv3x3_skip": ([_P, _P, _P],),
     "pmi_gemm_f32": ([C.POINTER(GemmF32Args), _P],),
     "pmi_softmax_f32": ([_P, _I, _I, _I, _F, _P],),
     "pmi_softmax_bwd_f32": ([_P, _P, _I, _I, _I, _F, _P],),

@@ -512,6 +512,51 @@ extern "C" int pmi_conv3x3_halo_config(const pmi_igemm_args* a) {
   return -1;
 }
 
+// ---- conv2 + skip in one launch (conv_wd.hip, skip segment) ----
+static int g_skip = 1;         // pmi_set_option(16, v): allow the fused launch (same-box A/B, c5 bf16: 38.59 -> 37.51 ms)
+void pmi_conv3x3_skip_enable(int v) { g_skip = v; }
+int pmi_conv3x3_wd_skip_launch(const pmi_igemm_args* a, const pmi_skip_args* k, int cfg, void* stream);
+int pmi_igemm_halo_allowed(void);
+// Tile config (6 / 7) of the fused launch, -1: not taken.  Both the answer and the config depend on the layer and the map only, never on the
+// number of images (a shard and its slice of a larger batch round alike): no workgroup count enters, and the split-K rule of the plain launch
+// is not consulted -- a fused launch is never split.  Cout % 256 == 0: the 256-channel tiles; else the 128-channel tiles, bf16 only -- the f16
+// 128-channel instantiation does not compile without scratch (profiles/conv_skip_kres.txt) and is not built.
+static int skip_config(const pmi_igemm_args* a, const pmi_skip_args* k) {
+  if (!a || !k || !g_skip || !g_wd || !g_wd_mf16 || !pmi_igemm_halo_allowed()) return -1;
+  if (!a->A0 || !a->D || !a->Bf || !k->X0 || !k->Wf) return -1;
+  if (((uintptr_t)a->A0 | (uintptr_t)a->A1 | (uintptr_t)a->D | (uintptr_t)a->Bf | (uintptr_t)k->X0 | (uintptr_t)k->X1 | (uintptr_t)k->Wf) & 15) return -1;   // 16-byte loads / stores
+  if (a->dtype != PMI_DT_F16 && a->dtype != PMI_DT_BF16) return -1;
+  if (a->taps != 9 || a->stride != 1 || a->batch > 1 || a->up || a->res_up || a->R || a->splitk > 1 || a->split_in || a->split_out) return -1;
+  if (a->out_f32 || a->res_f32 || a->D2 || a->aux || a->alpha != 1.f || a->act != PMI_ACT_NONE) return -1;
+  if (!a->pro_a || !a->pro_b || a->pro_act != PMI_ACT_SILU) return -1;
+  if (a->M <= 0 || a->H <= 0 || a->W <= 0 || a->Hin != a->H || a->Win != a->W || (a->M % (a->H * a->W)) || (a->W % 32) || (a->H % 8)) return -1;
+  if (a->N <= 0 || (a->N % 128) || (a->ldd & 7) || a->ldd < a->N) return -1;
+  const int Cin = a->C0 + a->C1;
+  if (Cin <= 0 || (Cin % 64) || (a->C0 % 64) || a->C1 < 0 || a->K != 9 * Cin || (a->lda0 & 7) || a->lda0 < a->C0) return -1;
+  if (a->C1 > 0 ? (!a->A1 || (a->lda1 & 7) || a->lda1 < a->C1) : a->A1 != nullptr) return -1;
+  if (a->nbias && a->hw <= 0) return -1;
+  if (k->C0 <= 0 || (k->C0 % 64) || k->C1 < 0 || (k->C1 % 64) || (k->ld0 & 7) || k->ld0 < k->C0) return -1;
+  if (k->C1 > 0 ? (!k->X1 || (k->ld1 & 7) || k->ld1 < k->C1) : k->X1 != nullptr) return -1;
+  if ((int64_t)a->H * a->W * (k->ld0 > k->ld1 ? k->ld0 : k->ld1) * 2 >= 0x7fffffffll) return -1;     // 32-bit byte offsets inside an image
+  int cfg;
+  if (g_force_cfg >= 0) {
+    cfg = g_force_cfg;                                   // (A/B and tests)
+    if (cfg != 6 && cfg != 7) return -1;
+  } else {
+    cfg = (a->N % 256) == 0 ? 6 : 7;
+  }
+  if (cfg == 6 && ((a->N % 256) || Cin > 2048)) return -1;
+  if (cfg == 7 && (a->dtype == PMI_DT_F16 || !g_wd128 || Cin > 1024)) return -1;
+  if (a->stats && a->stats_p != (a->H / 8) * (a->W / 32)) return -1;
+  return cfg;
+}
+extern "C" int pmi_conv3x3_skip_eligible(const pmi_igemm_args* a, const pmi_skip_args* k) { const int cfg = skip_config(a, k); return cfg >= 0 ? cfg : 0; }
+extern "C" int pmi_conv3x3_skip(const pmi_igemm_args* a, const pmi_skip_args* k, pmi_stream_t stream) {
+  const int cfg = skip_config(a, k);
+  if (cfg < 0) return PMI_ERR_ARG;
+  return pmi_conv3x3_wd_skip_launch(a, k, cfg, stream);
+}
+
 int pmi_conv3x3_halo_launch(const pmi_igemm_args* a, int cfg, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   return a->dtype == PMI_DT_BF16 ? launch_t<BF16>(*a, s, cfg) : launch_t<F16>(*a, s, cfg);

@@ -76,8 +76,13 @@ constexpr int cmax(int a, int b) { return a > b ? a : b; }
 //   SIN = 1: doubled operand: the result is split again, y = yh + yl, and a chunk's K is [yh of CK/2 logical channels | their yl] against
 //            weights duplicated in the same pattern (W*yh + W*yl in fp32: an fp32-grade product at twice the MFMA work).
 // (PRO = 0 over a split input needs neither: its 2C physical channels are an ordinary K dimension, SIN = 0.)
-template <typename T, int PRO, bool MF16, int NWN = 8, int CK = 64, bool SPL = false, bool SK = false, bool SMALLC = false, int SIN = 0>
-__global__ __launch_bounds__(NWN * 64, 2) void conv3x3_wd_kernel(const pmi_igemm_args a) {
+// SKIP (pmi_conv3x3_skip, configs 6 / 7 with a fused SiLU prologue): the ResBlock's two-source 1x1 skip convolution as extra K behind the
+// last nine-tap chunk -- the tile's own 256 pixels of x0 | x1, staged RAW (no coefficients, no activation), against centre-tap weights
+// (see the skip segment below).  Its own instantiations (SKIP): the plain ones compile to the code they had before the segment existed.
+template <bool SKIP> struct wd_skip_arg {};                                   // the plain instantiations carry no second argument
+template <> struct wd_skip_arg<true> { pmi_skip_args k; };
+template <typename T, int PRO, bool MF16, int NWN = 8, int CK = 64, bool SPL = false, bool SK = false, bool SMALLC = false, int SIN = 0, bool SKIP = false>
+__global__ __launch_bounds__(NWN * 64, 2) void conv3x3_wd_kernel(const pmi_igemm_args a, const wd_skip_arg<SKIP> skq) {
   static_assert(SIN == 0 || (PRO != 0 && MF16 && !SK && !SMALLC && std::is_same<T, F16>::value), "split-input staging: fused prologue, f16, 16x16x32 tiles");
   constexpr int NW = NWN, NT = NW * 64;
   constexpr int KS = MF16 ? CK / 32 : CK / 16;         // k-steps (one MFMA deep) per chunk
@@ -499,6 +504,80 @@ __global__ __launch_bounds__(NWN * 64, 2) void conv3x3_wd_kernel(const pmi_igemm
     }
    }
   }
+  if constexpr (SKIP) {
+    // ---- skip segment: acc += W_s * (x0 | x1) over the tile's own pixels (guided_diffusion/unet.py ResBlock.skip_connection over the
+    // th.cat of :650-652).  The patch buffers are free (the main loop's last barrier is behind every read a wave still uses); they now hold
+    // two dense buffers of 256 pixels x CK channels at the patch's row pitch, so a fragment read is again (per-lane base) + (constant).
+    // Per CK-channel chunk: one barrier, KS k-steps of 32 MFMAs per wave against 2 KS weight fragments streamed a chunk ahead; the
+    // chunk's pixels were loaded two chunks ahead into registers and written to the other buffer one chunk ahead.  Chunks past the
+    // end load nothing (out-of-range offsets) and are never multiplied.
+    static_assert(MF16 && PRO != 0 && !SPL && !SK && !SMALLC && SIN == 0, "skip segment: 16-bit 16x16x32 tiles with a fused prologue");
+    constexpr int SBUF = NPX * ROW;                      // one skip buffer
+    constexpr int NSP = NPX * CPR / NT;                  // 16-byte pieces per thread and chunk (4)
+    static_assert(NT / CPR == 64 && NSP * 64 == NPX && SBUF <= PATCH_BYTES, "skip staging: 64 pixels per pass, inside the patch buffers");
+    const pmi_skip_args& k = skq.k;
+    const int nsk = (k.C0 + k.C1) / CK;
+    const int64_t hw = (int64_t)a.H * a.W;
+    const u16* const X0i = (const u16*)k.X0 + (int64_t)img * hw * k.ld0;
+    const u16* const X1i = k.X1 ? (const u16*)k.X1 + (int64_t)img * hw * k.ld1 : X0i;
+    const int64_t xb0 = ((hw - 1) * k.ld0 + k.C0) * 2, xb1 = k.X1 ? ((hw - 1) * k.ld1 + k.C1) * 2 : 0;
+    const int sp = tid / CPR;                            // this thread's pixel inside a pass of 64 (two tile rows)
+    const int spix = (y0 + (sp >> 5)) * a.W + x0 + (sp & 31);
+    struct SPiece { uint4 v[NSP]; };
+    auto load_s = [&](int c) -> SPiece {
+      SPiece r;
+      const int cbase = c * CK;
+      const bool second = cbase >= k.C0;                 // wave-uniform: C0 is a multiple of CK
+      const __amdgpu_buffer_rsrc_t rs = make_rsrc(second ? X1i : X0i, second ? xb1 : xb0);
+      const uint32_t ld2 = (uint32_t)(second ? k.ld1 : k.ld0) * 2u;
+      const uint32_t so = (uint32_t)(cbase - (second ? k.C0 : 0)) * 2u;
+#pragma unroll
+      for (int j = 0; j < NSP; ++j)
+        r.v[j] = buf_load16(rs, c < nsk ? (uint32_t)(spix + 2 * j * a.W) * ld2 + (uint32_t)sc * 16u : PMI_BUF_OOB, so);
+      return r;
+    };
+    auto write_s = [&](char* buf, const SPiece& p) {
+#pragma unroll
+      for (int j = 0; j < NSP; ++j) *(uint4*)(buf + (sp + 64 * j) * ROW + sc * 16) = p.v[j];
+    };
+    // this wave's skip weights: [chunk][k-step][16-channel block][lane][8] 16-bit, contiguous in loop order
+    const int64_t sslab = (int64_t)nsk * KS * 2048;
+    const __amdgpu_buffer_rsrc_t rsrc_s = make_rsrc((const char*)k.Wf + (wave_live ? (int64_t)(tn * NWN + wn) * sslab : 0), wave_live ? sslab : 0);
+    uint4 sw[KS][2], swn[KS][2];
+    auto load_sw = [&](uint4 (&w)[KS][2], int c) {       // (past the last chunk: outside the resource, zeros)
+#pragma unroll
+      for (int s_ = 0; s_ < KS; ++s_)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) w[s_][cb] = buf_load16(rsrc_s, wvo + (uint32_t)((c * KS + s_) * 2 + cb) * 1024u, 0);
+    };
+    __builtin_amdgcn_sched_barrier(0);
+    SPiece pa = load_s(0), pq = load_s(1);
+    load_sw(sw, 0);
+    write_s(smem, pa);
+    pa = pq; pq = load_s(2);
+    for (int c = 0; c < nsk; ++c) {
+      load_sw(swn, c + 1);
+      __syncthreads();                                   // chunk c is complete in its buffer; every wave is done with the other one
+      const char* const sb = smem + (c & 1) * SBUF + frag0;
+#pragma unroll
+      for (int s_ = 0; s_ < KS; ++s_)
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+          for (int sx = 0; sx < 2; ++sx) {
+            const uint4 x = *(const uint4*)(sb + (i * 32 + sx * 16) * ROW + s_ * 64);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) acc4[i][sx][cb] = T::mfma16(sw[s_][cb], x, acc4[i][sx][cb]);
+          }
+      write_s(smem + ((c + 1) & 1) * SBUF, pa);
+      pa = pq; pq = load_s(c + 3);
+#pragma unroll
+      for (int s_ = 0; s_ < KS; ++s_)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) sw[s_][cb] = swn[s_][cb];
+    }
+    __syncthreads();                                     // the epilogue's staging overwrites the skip buffers
+  }
 
   }
   CSTAMP(1);
@@ -674,7 +753,12 @@ __global__ __launch_bounds__(NWN * 64, 2) void conv3x3_wd_kernel(const pmi_igemm
   const __amdgpu_buffer_rsrc_t rs_d = make_rsrc((u16*)a.D + (int64_t)img * a.H * a.W * a.ldd, ((int64_t)(a.H * a.W - 1) * a.ldd + a.N) * 2);
   const uint32_t rvo = col_live ? (uint32_t)((psub >> rup) * a.ldr + n0 + cl0) * 2u : PMI_BUF_OOB;
   const uint32_t dvo = col_live ? (uint32_t)(psub * a.ldd + n0 + cl0) * 2u : PMI_BUF_OOB;
-  uint4 rres[NWI];
+  // a fused conv2 + skip launch has no residual (R is NULL).  The 256-channel tile drops the loads there: with them its epilogue spilled 19
+  // registers; the 128-channel tile keeps them (empty resource: no traffic) -- without them ITS allocation spilled 5 in the main loop.
+  // (Register allocation of one compiler, ROCm 7's clang: profiles/conv_skip_kres.txt is the check to repeat when the toolchain changes.)
+  constexpr bool NORES = SKIP && NWN == 8;
+  uint4 rres[NORES ? 1 : NWI];
+  if constexpr (!NORES)
 #pragma unroll
   for (int t = 0; t < NWI; ++t) {                      // residual loads fly while the accumulators are staged
     const int pu = wid * PXW + t * PPI;                // the instruction's first pixel (wave-uniform; PPI divides 32, so pu & 31 is even for PPI >= 2)
@@ -731,12 +815,12 @@ __global__ __launch_bounds__(NWN * 64, 2) void conv3x3_wd_kernel(const pmi_igemm
   for (int t = 0; t < NWI; ++t) {
     const int p = wid * PXW + t * PPI + psub;
     uint4 v = *(const uint4*)(stg + p * SROW + cl0 * 2);
-    if (a.R || a.stats) {
+    if ((!NORES && a.R) || a.stats) {
       float f[8];
       unpack8<T>(v, f);
-      if (a.R) {
+      if (!NORES && a.R) {
         float r[8];
-        unpack8<T>(rres[t], r);
+        unpack8<T>(rres[NORES ? 0 : t], r);
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] += r[e];
         v = pack8<T>(f);
@@ -788,18 +872,18 @@ int launch_p(const pmi_igemm_args& a, hipStream_t s, int cfg) {
     if (cfg != 6 && cfg != 7 && !(cfg == 8 && PRO == 0)) return PMI_ERR_ARG;
     if constexpr (PRO == 0) {
       if (a.split_in == 2) return PMI_ERR_ARG;
-      if (cfg == 8) hipLaunchKernelGGL((conv3x3_wd_kernel<T, 0, true, 4, 32, true, false, true>), g7, dim3(256), 0, s, a);      // first convolution, split output
-      else if (cfg == 7) hipLaunchKernelGGL((conv3x3_wd_kernel<T, 0, true, 4, 32, true>), g7, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((conv3x3_wd_kernel<T, 0, true, 8, 64, true>), g6, dim3(512), 0, s, a);
+      if (cfg == 8) hipLaunchKernelGGL((conv3x3_wd_kernel<T, 0, true, 4, 32, true, false, true>), g7, dim3(256), 0, s, a, wd_skip_arg<false>{});      // first convolution, split output
+      else if (cfg == 7) hipLaunchKernelGGL((conv3x3_wd_kernel<T, 0, true, 4, 32, true>), g7, dim3(256), 0, s, a, wd_skip_arg<false>{});
+      else hipLaunchKernelGGL((conv3x3_wd_kernel<T, 0, true, 8, 64, true>), g6, dim3(512), 0, s, a, wd_skip_arg<false>{});
     } else if constexpr (PRO == 1 + PMI_ACT_SILU && std::is_same<T, F16>::value) {
       // fused GroupNorm-apply + SiLU over a split input: the doubled operand (split_in 1) or the single operand (split_in 2)
       if (a.split_in != 1 && a.split_in != 2) return PMI_ERR_ARG;
       if (cfg == 7) {
-        if (a.split_in == 1) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 4, 32, true, false, false, 1>), g7, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 4, 32, true, false, false, 2>), g7, dim3(256), 0, s, a);
+        if (a.split_in == 1) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 4, 32, true, false, false, 1>), g7, dim3(256), 0, s, a, wd_skip_arg<false>{});
+        else hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 4, 32, true, false, false, 2>), g7, dim3(256), 0, s, a, wd_skip_arg<false>{});
       } else {
-        if (a.split_in == 1) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 8, 64, true, false, false, 1>), g6, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 8, 64, true, false, false, 2>), g6, dim3(512), 0, s, a);
+        if (a.split_in == 1) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 8, 64, true, false, false, 1>), g6, dim3(512), 0, s, a, wd_skip_arg<false>{});
+        else hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 8, 64, true, false, false, 2>), g6, dim3(512), 0, s, a, wd_skip_arg<false>{});
       }
     } else {
       return PMI_ERR_ARG;
@@ -810,7 +894,7 @@ int launch_p(const pmi_igemm_args& a, hipStream_t s, int cfg) {
   if (a.split_in) return PMI_ERR_ARG;
   if (cfg == 8) {                                      // at most 32 input channels (first convolution): PRO == 0 only
     if constexpr (PRO == 0) {
-      hipLaunchKernelGGL((conv3x3_wd_kernel<T, 0, true, 4, 32, false, false, true>), dim3(nimg * (a.H / 8) * (a.W / 32) * ((a.N + 127) / 128)), dim3(256), 0, s, a);
+      hipLaunchKernelGGL((conv3x3_wd_kernel<T, 0, true, 4, 32, false, false, true>), dim3(nimg * (a.H / 8) * (a.W / 32) * ((a.N + 127) / 128)), dim3(256), 0, s, a, wd_skip_arg<false>{});
       PMI_CHECK_LAUNCH();
       return PMI_OK;
     }
@@ -818,15 +902,15 @@ int launch_p(const pmi_igemm_args& a, hipStream_t s, int cfg) {
   }
   if (cfg == 7) {                                      // 128-channel tiles, two 4-wave workgroups per CU
     const int t7 = nimg * (a.H / 8) * (a.W / 32) * ((a.N + 127) / 128);
-    if (a.splitk > 1) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 4, 32, false, true>), dim3(t7, 1, a.splitk), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 4, 32>), dim3(t7), dim3(256), 0, s, a);
+    if (a.splitk > 1) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 4, 32, false, true>), dim3(t7, 1, a.splitk), dim3(256), 0, s, a, wd_skip_arg<false>{});
+    else hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 4, 32>), dim3(t7), dim3(256), 0, s, a, wd_skip_arg<false>{});
     PMI_CHECK_LAUNCH();
     return PMI_OK;
   }
   const int tiles = nimg * (a.H / 8) * (a.W / 32) * (a.N / 256);
-  if (cfg == 6 && a.splitk > 1) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 8, 64, false, true>), dim3(tiles, 1, a.splitk), dim3(512), 0, s, a);
-  else if (cfg == 6) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true>), dim3(tiles), dim3(512), 0, s, a);    // v_mfma_f32_16x16x32
-  else hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, false>), dim3(tiles), dim3(512), 0, s, a);             // config 4: 32x32x16
+  if (cfg == 6 && a.splitk > 1) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true, 8, 64, false, true>), dim3(tiles, 1, a.splitk), dim3(512), 0, s, a, wd_skip_arg<false>{});
+  else if (cfg == 6) hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, true>), dim3(tiles), dim3(512), 0, s, a, wd_skip_arg<false>{});    // v_mfma_f32_16x16x32
+  else hipLaunchKernelGGL((conv3x3_wd_kernel<T, PRO, false>), dim3(tiles), dim3(512), 0, s, a, wd_skip_arg<false>{});             // config 4: 32x32x16
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
@@ -870,6 +954,27 @@ int pmi_conv3x3_wd_splitk(const pmi_igemm_args* a, int cfg) {
 // (Also measured and removed in round 3: split-output tiles starting their accumulators from the residual, loaded by each lane for its own
 // accumulator elements before the prologue, so that the epilogue's write-out is stores only.  The epilogue went 33.6 -> 20.9 us per tile but the
 // 8-byte accumulator-layout loads took 22 us of prologue: c5 mixed step 63.0 -> 64.6 ms on one box.)
+// The fused conv2 + skip launch of pmi_conv3x3_skip (conv3x3.hip checks the arguments): the tile-to-workgroup mapping is the plain launch's.
+template <typename T>
+static int launch_skip(const pmi_igemm_args& a, const pmi_skip_args& k, hipStream_t s, int cfg) {
+  const int t8 = a.M / (a.H * a.W) * (a.H / 8) * (a.W / 32);
+  // configs 7 (4 waves, 32-channel chunks) and 6 (8 waves, 64-channel chunks) with the skip segment: SiLU prologue, plain 16-bit epilogue
+  constexpr int P = 1 + PMI_ACT_SILU;
+  const wd_skip_arg<true> q{k};
+  if (cfg == 7) {
+    // (bf16 only: the f16 form of this tile carries 28 B / lane of scratch with the segment, so it is not built and conv3x3.hip refuses the call)
+    if constexpr (std::is_same<T, BF16>::value) hipLaunchKernelGGL((conv3x3_wd_kernel<T, P, true, 4, 32, false, false, false, 0, true>), dim3(t8 * (a.N / 128)), dim3(256), 0, s, a, q);
+    else return PMI_ERR_ARG;
+  } else if (cfg == 6) hipLaunchKernelGGL((conv3x3_wd_kernel<T, P, true, 8, 64, false, false, false, 0, true>), dim3(t8 * (a.N / 256)), dim3(512), 0, s, a, q);
+  else return PMI_ERR_ARG;
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+int pmi_conv3x3_wd_skip_launch(const pmi_igemm_args* a, const pmi_skip_args* k, int cfg, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  return a->dtype == PMI_DT_BF16 ? launch_skip<BF16>(*a, *k, s, cfg) : launch_skip<F16>(*a, *k, s, cfg);
+}
+
 int pmi_conv3x3_wd_launch(const pmi_igemm_args* a, int cfg, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   return a->dtype == PMI_DT_BF16 ? launch_t<BF16>(*a, s, cfg) : launch_t<F16>(*a, s, cfg);

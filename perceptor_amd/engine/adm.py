@@ -191,6 +191,8 @@ class AdmEngine:
                     self.w[p + ".conv2"] = lin(p + ".out_layers.3")
                     if l.cin != l.cout:
                         self.w[p + ".skip"] = lin(p + ".skip_connection", sources=l.srcs)
+                        if self._skip_fusable(l):
+                            self.w[p + ".skip.b"] = ops.fused_skip_bias(self.w[p + ".conv2"], self.w[p + ".skip"])
                     l.emb_off = off
                     emb_w.append(sd[p + ".emb_layers.1.weight"].float()); emb_b.append(sd[p + ".emb_layers.1.bias"].float())
                     off += emb_w[-1].shape[0]
@@ -209,6 +211,26 @@ class AdmEngine:
         self.conv_out = lin("out.2")
 
     # ---- blocks ----------------------------------------------------------------------------------
+    def _skip_fusable(self, l: _Res) -> bool:
+        """Structure of a ResBlock whose two-source skip convolution can ride in its conv2 launch (ops.igemm(skip=...)): 16-bit modes, a
+        concatenated input, no resampling, channel counts the 128-channel tiles divide.  The map size joins in _conv2 (SKIP_FUSE_MIN_HW)."""
+        return not self.precise and l.srcs is not None and l.cin != l.cout and not l.up and not l.down \
+            and l.cout % 128 == 0 and all(c % 64 == 0 for c in l.srcs)
+
+    def _conv2(self, l: _Res, h, x, x1, prologue):
+        """out_layers' convolution + the skip path (unet.py:232-252): one fused launch where the block and the map allow, else the skip
+        GEMM and conv2 with its output as the residual.  The choice depends on the layer, the dtype and the map size only, never on the batch
+        (pmi_conv3x3_skip_eligible counts no workgroups; f16 layers with cout % 256 != 0 keep the two launches)."""
+        w = self.w
+        if l.cin != l.cout:
+            sb = w.get(l.p + ".skip.b")
+            if sb is not None and h.shape[1] * h.shape[2] >= ops.SKIP_FUSE_MIN_HW and h.shape[1] % 8 == 0 and h.shape[2] % 32 == 0:
+                return ops.igemm(h, w[l.p + ".conv2"], prologue=prologue, want_stats=True, skip=(w[l.p + ".skip"], x, x1, sb))
+            x = ops.igemm(x, w[l.p + ".skip"], a1=x1)
+        elif x1 is not None:
+            raise NotImplementedError("identity skip over a concatenated input does not occur in the shipped configs")
+        return ops.igemm(h, w[l.p + ".conv2"], residual=x, res_up=l.up, prologue=prologue, want_stats=True)
+
     def _res(self, l: _Res, x, x1, emb):
         cfg, dt, w = self.cfg, self.dt, self.w
         g1, b1 = w[l.p + ".gn1"]
@@ -233,11 +255,7 @@ class AdmEngine:
             ca, cb = ops.group_norm_coeffs(h, g2, b2, 32, dt, film=e, film_ld=emb.stride(0))
         else:
             ca, cb = ops.group_norm_coeffs(h, g2, b2, 32, dt)
-        if l.cin != l.cout:
-            skip = ops.igemm(skip, w[l.p + ".skip"], a1=skip1)
-        elif skip1 is not None:
-            raise NotImplementedError("identity skip over a concatenated input does not occur in the shipped configs")
-        return ops.igemm(h, w[l.p + ".conv2"], residual=skip, res_up=l.up, prologue=(ca, cb, ACT_SILU), want_stats=True)
+        return self._conv2(l, h, skip, skip1, (ca, cb, ACT_SILU))
 
     def _attn(self, l: _Attn, x):
         dt, w = self.dt, self.w
@@ -356,11 +374,7 @@ class AdmEngine:
         g2, b2 = w[l.p + ".gn2"]
         film = e if cfg.use_scale_shift_norm else None
         ca2, cb2, parts2 = ops.group_norm_coeffs_train(h, g2, b2, 32, dt, film=film, film_ld=emb.stride(0) if film is not None else 0)
-        if l.cin != l.cout:
-            skip = ops.igemm(skip, w[l.p + ".skip"], a1=skip1)
-        elif skip1 is not None:
-            raise NotImplementedError("identity skip over a concatenated input does not occur in the shipped configs")
-        out = ops.igemm(h, w[l.p + ".conv2"], residual=skip, res_up=l.up, prologue=(ca2, cb2, ACT_SILU), want_stats=True)
+        out = self._conv2(l, h, skip, skip1, (ca2, cb2, ACT_SILU))
         tape.append(("res", l, x, x1, (ca, cb, parts), h, (ca2, cb2, parts2), film))
         return out
 

@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from .. import _hip
-from .._hip import ACT_GEGLU, ACT_NONE, DT_F16X2, IgemmArgs, call, ptr
+from .._hip import ACT_GEGLU, ACT_NONE, DT_F16X2, IgemmArgs, SkipArgs, call, ptr
 
 
 HALO_ENABLED = True
@@ -22,6 +22,9 @@ SPLITK_ENABLED = True
 WD_ENABLED = True       # weights-direct conv3x3 kernel (csrc/conv_wd.hip) where the shape is eligible
 GEMM_WD_ENABLED = True       # weights-direct GEMM (csrc/gemm_wd.hip) for plain GEMMs
 GEMM_WD_CONV = os.environ.get("PMI_GEMM_WD_CONV", "1") != "0"   # A-B switch: small-map 3x3 convolutions on the weights-direct GEMM (csrc/gemm_wd.hip, CONV)
+# Smallest map (pixels per image) on which a ResBlock's two-source 1x1 skip convolution is folded into its conv2 launch (pmi_conv3x3_skip);
+# smaller maps keep the separate skip GEMM.  Set per level by measurement (profiles/conv_skip_ab.txt); structural, never a function of the batch.
+SKIP_FUSE_MIN_HW = 64 * 64
 FLASH_ENABLED = True    # general flash attention (csrc/attn_flash.hip) instead of batched GEMMs + softmax where the head dim is not 64
 
 
@@ -192,6 +195,16 @@ class PackedLinear:
             self._frag[key] = w.permute(0, 5, 4, 6, 3, 1, 7, 2, 8).contiguous()
         return self._frag[key]
 
+    def frag_skip(self) -> torch.Tensor:
+        """A 1x1 (two-source) skip convolution's weights for the skip segment of the weights-direct conv3x3 (csrc/conv_wd.hip, pmi_conv3x3_skip):
+        the centre tap only, k = the concatenated channel index, in the 16x16x32 fragment order of frag16 without its tap dimensions:
+        [N/32][K/32][16-channel block][lane = 16*(k quarter) + channel][8 k] -- one order for both chunk sizes (ck = 32 / 64)."""
+        if "skip" not in self._frag:
+            assert self.taps == 1 and not self.split and self.n_p % 32 == 0 and self.K % 64 == 0
+            w = self.w.view(self.n_p // 32, 2, 16, self.K // 32, 4, 8)        # nb, cb, r16, k32, q4, j
+            self._frag["skip"] = w.permute(0, 3, 1, 4, 2, 5).contiguous()
+        return self._frag["skip"]
+
     def frag_c8(self) -> torch.Tensor:
         """Fragment order for config 8 of the weights-direct kernel (at most 32 input channels): k = tap * Cin + c zero-padded to whole
         32-deep MFMA steps, [N/32][steps][16-channel block (2)][lane = 16*(k quarter) + channel][8 k]."""
@@ -237,6 +250,16 @@ class MixedLinear:
             w, b, dev, src, cp = self._args
             self._dbl = PackedLinear(w, b, DT_F16X2, dev, cin_pad=cp, sources=src, concat_sources=False)
         return self._dbl
+
+
+def fused_skip_bias(conv: PackedLinear, skip: PackedLinear) -> torch.Tensor:
+    """Bias table of the fused conv2 + skip launch: the two layers' biases added once, in fp32, when the weights are packed."""
+    assert conv.n_p == skip.n_p
+    b = torch.zeros(conv.n_p, dtype=torch.float32, device=conv.w.device)
+    for lin in (conv, skip):
+        if lin.b is not None:
+            b += lin.b
+    return b
 
 
 # ---- input gradients: dX of a convolution is the forward kernel on transposed + flipped weights -------------------------------------
@@ -386,8 +409,12 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
           out_f32: bool = False, out: Optional[torch.Tensor] = None, alpha: float = 1.0, prologue=None,
           want_stats: bool = False, hw: Optional[int] = None, pre_out: Optional[torch.Tensor] = None,
           act_grad_of: Optional[torch.Tensor] = None, act_grad: int = ACT_NONE, defer_reduce: bool = False,
-          split_out: bool = False) -> torch.Tensor:
+          split_out: bool = False, skip=None) -> torch.Tensor:
     """Convolution (a0 is [N,H,W,C]) or linear (a0 is [M,C]) through pmi_igemm.
+
+    skip = (skip_lin, x0, x1, bias): a ResBlock's conv2 whose residual is the 1x1 convolution skip_lin over x0 | x1 (x1 may be None);
+    bias = fused_skip_bias(lin, skip_lin).  Where pmi_conv3x3_skip takes the shape the product is accumulated inside this launch; otherwise
+    the skip GEMM runs on its own and its output is the residual, as without the argument.
 
     prologue = (coef_a [N,Cin], coef_b [N,Cin], act): fused GroupNorm-apply(+FiLM)+activation on the conv input
     (LDS-halo conv3x3 kernel only); when the shape is not eligible the apply kernel runs first.
@@ -436,6 +463,7 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
     a.ldnb = nbias.stride(0) if nbias is not None else 0
     a.batch, a.batch_inner = 1, 1
     a.dtype = dt
+    cfg = -1
     if conv and lin.taps == 9 and stride == 1 and HALO_ENABLED and WD_ENABLED and lin.n_p % 32 == 0 and ((lin.n_p >= 128 and lin.cin_p % 64 == 0) or (lin.cin_p <= 32 and a1 is None)):
         a.Bf = 1                       # ask which tile config the weights-direct kernel would run, then hand it that packing
         a.pro_a = 1 if (prologue is not None and not lin.split) else None     # (the table size limit depends on a fused prologue)
@@ -458,7 +486,31 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
         a.Bf = ptr(lin.frag_gemm()) if _hip.lib().pmi_gemm_wd_eligible(C.byref(a)) else None      # ... and only then pack its weight order
         if a.Bf:
             want_stats = False
-    if prologue is not None:
+    fused_skip, k = False, None
+    if skip is not None:
+        slin, s0, s1, sbias = skip
+        assert residual is None and conv and prologue is not None
+        if act == ACT_NONE and a1 is None and HALO_ENABLED and WD_ENABLED and not lin.split and not slin.split and slin.taps == 1 and slin.n_p == lin.n_p \
+                and lin.n_p % 128 == 0 and lin.cin_p % 64 == 0 and slin.K % 64 == 0:
+            k = SkipArgs()
+            k.X0, k.X1, k.Wf = ptr(s0), ptr(s1), ptr(slin.frag_skip())
+            k.C0, k.C1 = s0.shape[-1], (s1.shape[-1] if s1 is not None else 0)
+            k.ld0, k.ld1 = s0.stride(-2), (s1.stride(-2) if s1 is not None else 0)
+            keep = (a.Bf, a.bias)
+            a.Bf = ptr(lin.w)   # (any pointer: the query names the tile config, a function of the layer and the map alone, and Bf follows it)
+            a.bias = ptr(sbias)
+            a.pro_a, a.pro_b, a.pro_act = ptr(prologue[0]), ptr(prologue[1]), prologue[2]
+            fcfg = _hip.lib().pmi_conv3x3_skip_eligible(C.byref(a), C.byref(k))
+            fused_skip = fcfg in (6, 7)
+            if fused_skip:
+                a.Bf = ptr(lin.frag16(64 if fcfg == 6 else 32))
+            else:
+                a.Bf, a.bias = keep
+                a.pro_a, a.pro_b, a.pro_act = None, None, 0
+        if not fused_skip:
+            residual = igemm(s0, slin, a1=s1)
+            a.R, a.ldr, a.res_f32 = ptr(residual), residual.stride(-2), 0
+    if prologue is not None and not fused_skip:
         ca, cb, pact = prologue
         if HALO_ENABLED and not lin.split and _hip.lib().pmi_conv3x3_halo_config(C.byref(a)) >= 0:
             a.pro_a, a.pro_b, a.pro_act = ptr(ca), ptr(cb), pact
@@ -482,7 +534,7 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
         a.Bf = 1           # a 3x3 convolution the conv3x3 kernels do not take (16x16 / 8x8 maps): the weights-direct GEMM's conv mode, if it does
         a.Bf = ptr(lin.frag_gemm()) if _hip.lib().pmi_gemm_wd_eligible(C.byref(a)) else None
         conv_gemm = bool(a.Bf)
-    if SPLITK_ENABLED:
+    if SPLITK_ENABLED and not fused_skip:
         sk = _hip.lib().pmi_igemm_splitk(C.byref(a))
         if sk > 1:   # few output tiles, long K: split the reduction over grid.z into fp32 slabs
             ws = _empty((sk, m, lin.n_p), torch.float32, a0.device)
@@ -495,7 +547,7 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
     if conv_gemm and (nbias is not None or res_up) and a.splitk <= 1:
         a.Bf = None            # a per-sample bias / up-sampled residual is the split-K reduce kernel's: unsplit, the generic kernel takes the call
     if want_stats:
-        rows = _hip.lib().pmi_igemm_stats_rows(C.byref(a))
+        rows = (a.H // 8) * (a.W // 32) if fused_skip else _hip.lib().pmi_igemm_stats_rows(C.byref(a))
         if rows > 0:   # fused per-channel (sum, sumsq) of the output for the next GroupNorm
             st = _empty((m // a.hw, rows, lin.n_p, 2), torch.float32, a0.device)
             a.stats, a.stats_p = ptr(st), rows
@@ -503,6 +555,19 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
     if DEBUG_WS is not None and a.splitk <= 1:      # (a split-K call's ws is its slab workspace: the phase stamps of the probes are for unsplit calls only)
         a.ws = ptr(DEBUG_WS)
         a.reserved = 77
+    if fused_skip:
+        if KERNEL_EVENTS is None:
+            call("pmi_conv3x3_skip", C.byref(a), C.byref(k))
+            return out
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call("pmi_conv3x3_skip", C.byref(a), C.byref(k))
+        e1.record()
+        # the plain launch's figures plus the skip product's: 2 M cin cout FLOP, its two sources and its weights read once
+        nbytes = a0.numel() * 2 + lin.w.numel() * 2 + out.numel() * out.element_size() + (s0.numel() + (s1.numel() if s1 is not None else 0)) * 2 + slin.w.numel() * 2
+        desc = f"{a.H}x{a.W} {c0}+{c1}->{lin.cout} cfg{fcfg} pro skip {k.C0}+{k.C1}{' stats' if want_stats else ''}"
+        KERNEL_EVENTS.append((e0, e1, 2.0 * m * lin.cout * (lin.cin * lin.taps + slin.cin), float(nbytes), desc))
+        return out
     if KERNEL_EVENTS is not None and lin.taps == 9 and HALO_ENABLED and _hip.lib().pmi_conv3x3_halo_config(C.byref(a)) >= 0:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
