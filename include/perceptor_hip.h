@@ -425,6 +425,30 @@ int pmi_rn_attn_fwd(const void* q, const void* kv, void* o, float* P, int N, int
 int pmi_rn_attn_bwd(const void* q, const void* kv, const float* P, const void* dout, void* dq, void* dkv, int N, int T, int C, int heads,
                     float scale, int dtype, pmi_stream_t s);
 
+/* ---- guidance losses beside the spherical CLIP loss (csrc/losses.hip), fp32, each with its gradient; no atomics: every scalar is a
+ * two-stage sum in a fixed order through the caller's `partial` workspace, so results are bit-identical from run to run.
+ * pmi_head_loss: a linear probe on the tower's un-normalised embedding emb [N][D], W [K][D], b [K] (K <= 16, D <= 4096); with
+ *   e = emb / max(|emb|, 1e-12), l = W e + b, p = softmax(l):
+ *   mode 0 (K = 1; losses/simulacra_aesthetic.py:36-41 over models/simulacra_aesthetic/simulacra_aesthetic.py:58-60, whose second
+ *     F.normalize is the identity): r = W (sqrt(D) e) + b, loss = mult * sum_n (r_n - target)^2 / n_total;
+ *   mode 1 "logit" (losses/aesthetic_visual_assessment.py:41-42): loss = -0.01 mult sum_n l[n][target - 1] / n_total;
+ *   mode 2 "expected" (:43-47): loss = 0.01 mult sum_n sum_k (p[n][k] (k + 1) - target)^2 / (n_total K) -- each of the K products is
+ *     squared on its own, as the reference does; they are NOT summed into an expectation first;
+ *   mode 3 "probability" (:48-49): loss = -mult sum_n p[n][target - 1] / n_total (modes 1 and 3: target an integer in 1 .. K).
+ *   out [N][K] = r (mode 0) or l; demb [N][D] = gscale * dloss/demb; n_total = global batch (>= N) as in pmi_spherical_loss;
+ *   partial = N floats.
+ * pmi_smoothness (losses/smoothness.py:5-10), x [N][C][H][W]: loss = sum (x[h+1] - x[h])^2 / (n_total C (H-1) W) +
+ *   sum (x[w+1] - x[w])^2 / (n_total C H (W-1)), grad = gscale * dloss/dx written in one pass; H < 2 or W < 2 is an argument error (the
+ *   reference yields NaN); partial = 2048 floats.
+ * pmi_sqdiff_loss (the tail of losses/resize.py:14-18): loss = sum (a - b)^2 / n_total_count, g = dloss/da = 2 (a - b) / n_total_count
+ *   (dloss/db = -g); n_total_count >= count is the global element count of a sharded batch; partial = 1024 floats. */
+int pmi_head_loss(const float* emb, const float* W, const float* b, float* loss, float* demb, float* out, float* partial, int N, int K,
+                  int D, int mode, float target, int n_total, float mult, float gscale, pmi_stream_t s);
+int pmi_smoothness(const float* x, float* loss, float* grad, float* partial, int N, int C, int H, int W, int n_total, float gscale,
+                   pmi_stream_t s);
+int pmi_sqdiff_loss(const float* a, const float* b, float* loss, float* g, float* partial, int64_t count, int64_t n_total_count,
+                    pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

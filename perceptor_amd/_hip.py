@@ -166,6 +166,10 @@ _PROTOS = {
     "pmi_rn_tokens_bwd": ([_P, _P, _P, _I, _I, _I, _I, _P],),
     "pmi_rn_attn_fwd": ([_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],),
     "pmi_rn_attn_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],),
+    # guidance losses (losses.hip)
+    "pmi_head_loss": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _F, _P],),
+    "pmi_smoothness": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],),
+    "pmi_sqdiff_loss": ([_P, _P, _P, _P, _P, _L, _L, _P],),
 }
 
 

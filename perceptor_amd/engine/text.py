@@ -26,6 +26,7 @@ TEXT_CONFIGS = {
     "ViT-B-32": (77, 49408, 512, 12, 8, 512),
     "ViT-B-16": (77, 49408, 512, 12, 8, 512),
     "ViT-L-14": (77, 49408, 768, 12, 12, 768),
+    "ViT-L-14-336": (77, 49408, 768, 12, 12, 768),
     "ViT-H-14": (77, 49408, 1024, 24, 16, 1024),
     "RN50": (77, 49408, 512, 12, 8, 1024),
     "RN101": (77, 49408, 512, 12, 8, 512),

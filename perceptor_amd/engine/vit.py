@@ -32,6 +32,7 @@ VIT_CONFIGS = {
     "ViT-B-32": (224, 32, 768, 12, 12, 512),
     "ViT-B-16": (224, 16, 768, 12, 12, 512),
     "ViT-L-14": (224, 14, 1024, 24, 16, 768),
+    "ViT-L-14-336": (336, 14, 1024, 24, 16, 768),   # 577 tokens
     "ViT-H-14": (224, 14, 1280, 32, 16, 1024),
 }
 

@@ -24,9 +24,11 @@ class LossInterface(torch.nn.Module):
         raise NotImplementedError(type(self).__name__ + ".forward")
 
 
-class _SphericalBase(LossInterface):
+class _TowerLoss(LossInterface):
+    """A loss on the embedding of ``self.model`` (a models.CLIP / models.OpenCLIP image tower).  A subclass supplies
+    ``_embedding_loss_and_grad(emb, n_total) -> (loss, gscale * dloss/d emb)`` on the un-normalised embedding [n, D]; that is also
+    what losses.tower_loss_and_grad asks of every term."""
     multiplier = 1.0
-    _normalize_targets = False
 
     @property
     def device(self):
@@ -36,6 +38,23 @@ class _SphericalBase(LossInterface):
         super().to(device)
         self.model.to(device)
         return self
+
+    def _embedding_loss_and_grad(self, emb, n_total):
+        raise NotImplementedError(type(self).__name__ + "._embedding_loss_and_grad")
+
+    @torch.no_grad()
+    def loss_and_grad(self, images, n_total=None):
+        """(loss, dloss/dimages).  ``n_total``: global batch when this rank holds a shard, so the
+        mean (and therefore the gradient) equals the single-process value (SURVEY.md §8e)."""
+        eng = self.model._need_engine()
+        images = images.to(self.device)
+        emb = eng.forward(images, save=True).contiguous()
+        loss, demb = self._embedding_loss_and_grad(emb, n_total)
+        return loss, eng.backward(demb)
+
+
+class _SphericalBase(_TowerLoss):
+    _normalize_targets = False
 
     def add_texts_(self, texts, weights=None):
         return self.add_encodings_(self.model.encode_texts(texts), weights)
@@ -64,21 +83,15 @@ class _SphericalBase(LossInterface):
         loss = (d * self.weights).mean()
         return loss.mul(self.multiplier) if self.multiplier != 1.0 else loss
 
-    @torch.no_grad()
-    def loss_and_grad(self, images, n_total=None):
-        """(loss, dloss/dimages).  ``n_total``: global batch when this rank holds a shard, so the
-        mean (and therefore the gradient) equals the single-process value (SURVEY.md §8e)."""
-        eng = self.model._need_engine()
-        images = images.to(self.device)
-        n = images.shape[0]
-        emb = eng.forward(images, save=True).contiguous()
+    def _embedding_loss_and_grad(self, emb, n_total):
+        n = emb.shape[0]
         k, dim = self.encodings.shape
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         demb = torch.empty_like(emb)
         enc, wts = self.encodings.data.contiguous(), self.weights.data.contiguous()
         call("pmi_spherical_loss", ptr(emb), ptr(enc), ptr(wts), ptr(loss), ptr(demb),
-             n, k, dim, int(n_total or n), float(self.multiplier), float(eng.gscale))
-        return loss[0], eng.backward(demb)
+             n, k, dim, int(n_total or n), float(self.multiplier), float(self.model._need_engine().gscale))
+        return loss[0], demb
 
 
 class OpenCLIP(_SphericalBase):

@@ -4,3 +4,4 @@ from .open_clip import CLIP, OpenCLIP
 from .velocity_diffusion import VelocityDiffusion
 from .stable_diffusion import StableDiffusion
 from .transformers_openai_clip import TransformersOpenAICLIP
+from .simulacra_aesthetic import SimulacraAesthetic
