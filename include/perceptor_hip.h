@@ -108,6 +108,8 @@ int pmi_conv3x3_halo_config(const pmi_igemm_args* a);
 /* 1 when the weights-direct GEMM (csrc/gemm_wd.hip) takes this call: plain GEMM (taps 1, one source, no per-sample bias / statistics / prologue),
  * K % 128 == 0, N % 256 == 0 and Bf = the weights in its fragment order [N/32][K/128][4][2][64 lanes][8] */
 int pmi_gemm_wd_eligible(const pmi_igemm_args* a);
+/* tile of the weights-direct GEMM launch for these arguments (splitk as it will be passed): rows * 1000 + columns (128 / 144 rows, 128 / 256 columns) */
+int pmi_gemm_wd_tile(const pmi_igemm_args* a);
 /* split-K factor recommended for this shape (1 = none); with splitk = S the caller passes ws = S*M*N floats */
 int pmi_igemm_splitk(const pmi_igemm_args* a);
 /* number of per-image partial rows the fused output statistics of this call would produce (0: not available for this shape) */

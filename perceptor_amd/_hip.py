@@ -72,6 +72,7 @@ _PROTOS = {
     "pmi_igemm_splitk": ([C.POINTER(IgemmArgs)],),
     "pmi_set_option": ([_I, _I],),
     "pmi_gemm_wd_eligible": ([C.POINTER(IgemmArgs)],),
+    "pmi_gemm_wd_tile": ([_P],),                   # (IgemmArgs by reference)
     "pmi_conv3x3_skip_eligible": ([_P, _P],),      # (IgemmArgs, SkipArgs by reference)
     "pmi_conv3x3_skip": ([_P, _P, _P],),
     "pmi_gemm_f32": ([C.POINTER(GemmF32Args), _P],),

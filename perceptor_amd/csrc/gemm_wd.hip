@@ -339,13 +339,18 @@ __global__ __launch_bounds__(NWV * 64, 2) void gemm_wd_kernel(const pmi_igemm_ar
 
 static int g_few_wgs = 128;        // A/B switch: pmi_set_option(12, n): 256-column grids below n workgroups use the 128-column tiles
 
+// columns per tile: 256 (eight waves), or 128 (four waves) for narrow / few-workgroup / half-filled-tail grids
+int tile_cols(const pmi_igemm_args& a) {
+  const bool few = a.splitk <= 1 && (long)((a.M + 127) / 128) * ((a.N + 255) / 256) < g_few_wgs && !a.D2 && !a.aux && a.act != PMI_ACT_GEGLU;
+  const bool half_tail = (a.N % 256) != 0 && (a.N % 256) <= 128 && a.N < 1024;     // e.g. N = 320: 3 tiles of 128 instead of 2 of 256 (one a quarter full)
+  return (a.N < 256 || few || half_tail) ? 128 : 256;
+}
+
 template <typename T>
 int launch(const pmi_igemm_args& a, hipStream_t s, int mb) {
   const int tm = 16 * mb;
   // fewer than 128 workgroups of 256 columns and no split-K (short K): the 128-column tiles double the grid (2056 x 1024 x 1024: 14.2 vs 16.7 us)
-  const bool few = a.splitk <= 1 && (long)((a.M + 127) / 128) * ((a.N + 255) / 256) < g_few_wgs && !a.D2 && !a.aux && a.act != PMI_ACT_GEGLU;
-  const bool half_tail = (a.N % 256) != 0 && (a.N % 256) <= 128 && a.N < 1024;     // e.g. N = 320: 3 tiles of 128 instead of 2 of 256 (one a quarter full)
-  if (a.N < 256 || few || half_tail) {                 // 128-column tiles, four waves, two workgroups per CU
+  if (tile_cols(a) == 128) {                           // 128-column tiles, four waves, two workgroups per CU
     const dim3 g4(((a.M + 127) / 128) * ((a.N + 127) / 128), 1, a.splitk > 1 ? a.splitk : 1);
     if (a.taps == 9) {
       if (a.A1) hipLaunchKernelGGL((gemm_wd_kernel<T, 8, true, 4, true>), g4, dim3(256), 0, s, a);
@@ -416,6 +421,12 @@ extern "C" int pmi_gemm_wd_eligible(const pmi_igemm_args* a) {
   if ((a->D2 || a->aux) && (a->out_f32 || a->splitk > 1 || (a->R && a->res_f32))) return 0;
   if (a->act == PMI_ACT_GEGLU && (a->R || a->D2 || a->aux || a->out_f32 || a->splitk > 1)) return 0;
   return 1;
+}
+
+// tile of the launch pmi_gemm_wd_launch would make for these arguments (a->splitk as it will be passed): rows * 1000 + columns
+extern "C" int pmi_gemm_wd_tile(const pmi_igemm_args* a) {
+  const int cols = tile_cols(*a);
+  return (cols == 128 ? 128 : pmi_gemm_wd_tile_rows(a, a->splitk)) * 1000 + cols;
 }
 
 int pmi_gemm_wd_launch(const pmi_igemm_args* a, void* stream) {

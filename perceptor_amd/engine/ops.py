@@ -404,6 +404,22 @@ def conv3x3_mixed(x: torch.Tensor, mlin: MixedLinear, *, operand: str, prologue,
     return out
 
 
+def _wd_tile_desc(a: IgemmArgs) -> str:
+    """GEMM_TRACE: the tile details the weights-direct GEMM's instantiations differ in (rows x columns per workgroup, two-source K, conv mode,
+    gated epilogue), as pmi_gemm_wd_tile reports them for the arguments of the launch."""
+    t = _hip.lib().pmi_gemm_wd_tile(C.byref(a))
+    return f" rows={t // 1000} cols={t % 1000}{' two' if a.A1 else ''}{' convmode' if a.taps == 9 else ''}{' geglu' if a.act == ACT_GEGLU else ''}"
+
+
+def _traced_call(name: str, args, desc: str, flops: float) -> None:
+    """One library call between two events, appended to GEMM_TRACE as (desc, flops, ev0, ev1)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    call(name, *args)
+    e1.record()
+    GEMM_TRACE.append((desc, flops, e0, e1))
+
+
 def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
           act: int = ACT_NONE, up: bool = False, stride: int = 1, res_up: bool = False, nbias: Optional[torch.Tensor] = None,
           out_f32: bool = False, out: Optional[torch.Tensor] = None, alpha: float = 1.0, prologue=None,
@@ -542,6 +558,10 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
             if defer_reduce and a.Bf and not conv and _hip.lib().pmi_gemm_wd_eligible(C.byref(a)):
                 # the caller fuses the reduction (+ bias / residual) into its next pass (LayerNorm): leave the raw slabs
                 a.reserved3 = 1
+                if GEMM_TRACE is not None:
+                    _traced_call("pmi_igemm", (C.byref(a),), f"gemm M={m} N={lin.n_p} K={lin.K} taps=1 splitk={sk} halo=-1 wd=1{_wd_tile_desc(a)} defer",
+                                 2.0 * m * lin.n_p * lin.K)
+                    return ("slabs", ws, sk)
                 call("pmi_igemm", C.byref(a))
                 return ("slabs", ws, sk)
     if conv_gemm and (nbias is not None or res_up) and a.splitk <= 1:
@@ -557,6 +577,11 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
         a.reserved = 77
     if fused_skip:
         if KERNEL_EVENTS is None:
+            if GEMM_TRACE is not None:
+                _traced_call("pmi_conv3x3_skip", (C.byref(a), C.byref(k)),
+                             f"conv M={m} N={lin.n_p} K={lin.K} taps=9 splitk=0 halo={fcfg} wd=0{' stats' if a.stats else ''} skip={k.C0}+{k.C1}",
+                             2.0 * m * lin.n_p * (lin.K + slin.K))
+                return out
             call("pmi_conv3x3_skip", C.byref(a), C.byref(k))
             return out
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -583,15 +608,13 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
         return out
     if GEMM_TRACE is not None:
         kind = "conv" if conv and (lin.taps == 9 or up or stride == 2) else "gemm"
+        wd = bool(a.Bf) and bool(_hip.lib().pmi_gemm_wd_eligible(C.byref(a)))
         desc = f"{kind} M={m} N={lin.n_p} K={lin.K} taps={lin.taps}{' up' if up else ''}{' s2' if stride == 2 else ''} splitk={a.splitk}" \
-               f" halo={_hip.lib().pmi_conv3x3_halo_config(C.byref(a)) if HALO_ENABLED else -1} wd={int(bool(a.Bf) and bool(_hip.lib().pmi_gemm_wd_eligible(C.byref(a))))}" \
+               f" halo={_hip.lib().pmi_conv3x3_halo_config(C.byref(a)) if HALO_ENABLED else -1} wd={int(wd)}" \
                f"{' res' if residual is not None else ''}{' f32out' if a.out_f32 else ''}{' nbias' if nbias is not None else ''}{' stats' if a.stats else ''}" \
-               f"{' split_in' if a.split_in else ''}{' split_out' if a.split_out else ''}{' self_concat' if lin.self_concat else ''}"
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call("pmi_igemm", C.byref(a))
-        e1.record()
-        GEMM_TRACE.append((desc, 2.0 * m * lin.n_p * lin.K, e0, e1))
+               f"{' split_in' if a.split_in else ''}{' split_out' if a.split_out else ''}{' self_concat' if lin.self_concat else ''}" \
+               f"{_wd_tile_desc(a) if wd else ''}"
+        _traced_call("pmi_igemm", (C.byref(a),), desc, 2.0 * m * lin.n_p * lin.K)
         return out
     call("pmi_igemm", C.byref(a))
     return out

@@ -78,6 +78,27 @@ def test_full_size_clip_guidance_gradient_shards_exactly(workload):
     assert bool(torch.isfinite(guided.predicted_noise).all())
 
 
+def test_full_size_bf16_routes_are_all_claimed_by_a_kernel_test(workload):
+    """One bf16 predicted_noise at the benchmark's size under GEMM_TRACE: every kernel route it takes is the claimed route of a case of
+    test_gpu_routes16.py (which holds it to float64 per element), or one of the routes listed there with the file that covers it."""
+    from perceptor_amd.engine import ops
+    import test_gpu_routes16 as T16
+    model, _, images, sched = workload
+    ops.GEMM_TRACE = []
+    try:
+        model.predicted_noise(images, sched[3][0])
+        torch.cuda.synchronize()
+        descs = [d for d, *_ in ops.GEMM_TRACE]
+    finally:
+        ops.GEMM_TRACE = None
+    assert descs, "nothing was traced"
+    keys = sorted({"bgemm" if d.startswith("bgemm ") else T16.census_key(T16.route16(d)) for d in descs})
+    owner = {k: ("tests/test_gpu_routes16.py (test_route16_bgemm)" if k == "bgemm" else T16.claimed_by(k)) for k in keys}
+    print(f"[routes16] census, {len(descs)} launches, {len(keys)} routes:\n  " + "\n  ".join(f"{k}  <-  {owner[k] or 'UNCLAIMED'}" for k in keys))
+    unclaimed = [k for k in keys if not owner[k]]
+    assert not unclaimed, f"routes of the full-size bf16 UNet that no kernel test claims: {unclaimed}"
+
+
 def test_graph_replay_of_a_guided_step_matches_eager_bit_for_bit():
     """engine/graph.py: the whole step (UNet -> CLIP gradient -> guidance -> DDIM) captured into a HIP graph, small config."""
     from perceptor_amd import losses, models
