@@ -969,7 +969,7 @@ def flash_attention_backward(saved, d_out: torch.Tensor, heads: int, d: int, dt:
     n, t = q.shape[:2]
     tk, c = k.shape[1], heads * d
     assert d_out.is_contiguous() and tuple(d_out.shape) == (n, t, c)
-    delta = torch.empty_like(lse)
+    delta = _empty(tuple(lse.shape), lse.dtype, lse.device)
     # cross-attention: k | v are the two halves of one [N, Tk, 2C] tensor (the forward's kv), the layout dkv is returned in
     if not dq_only and k.stride(1) == 2 * c and v.data_ptr() == k.data_ptr() + c * k.element_size():
         kib = _hip.lib().pmi_attn_flash_bwd_kv_workspace(n, t, tk, heads, d)

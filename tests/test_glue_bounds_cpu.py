@@ -220,7 +220,6 @@ def test_argument_guards(lib):
 # Entry points that no GPU test calls by name: the wrapper that calls them and the GPU test file that uses the wrapper.
 VIA_WRAPPER = {
     "pmi_gemm_f32": ("ops.gemm_f32", "test_gpu_precise_kernels.py"),
-    "pmi_attn_flash_train": ("ops.flash_attention_train", "test_gpu_sd_unet_grad.py"),
     "pmi_geglu_bwd": ("ops.geglu_backward", "test_gpu_sd_unet_grad.py"),
 }
 # Queries answered on the host without a launch: a CPU test file may name them instead.
