@@ -19,7 +19,6 @@ from .._hip import ACT_GEGLU, ACT_NONE, DT_F16X2, IgemmArgs, SkipArgs, call, ptr
 
 HALO_ENABLED = True
 SPLITK_ENABLED = True
-WD_ENABLED = True       # weights-direct conv3x3 kernel (csrc/conv_wd.hip) where the shape is eligible
 GEMM_WD_ENABLED = True       # weights-direct GEMM (csrc/gemm_wd.hip) for plain GEMMs
 GEMM_WD_CONV = os.environ.get("PMI_GEMM_WD_CONV", "1") != "0"   # A-B switch: small-map 3x3 convolutions on the weights-direct GEMM (csrc/gemm_wd.hip, CONV)
 # Smallest map (pixels per image) on which a ResBlock's two-source 1x1 skip convolution is folded into its conv2 launch (pmi_conv3x3_skip);
@@ -343,6 +342,89 @@ def split_convert(x: torch.Tensor, to_split: bool) -> torch.Tensor:
 
 
 MIXED_TRACE = None      # tools / tests: list collecting (route, operand, shape) of every conv3x3_mixed call
+_MARK = 1               # a pointer that is not there yet in a host query (_as_if): the C ABI tests such fields against NULL only
+
+
+def _igemm_args(lin: PackedLinear, m: int, a0: Optional[torch.Tensor] = None, a1: Optional[torch.Tensor] = None, c0: Optional[int] = None,
+                c1: int = 0, *, out=None, residual=None, nbias=None, grid=None, hw: int = 1, stride: int = 1, up: int = 0, res_up: bool = False,
+                act: int = ACT_NONE, alpha: float = 1.0, split_out: int = 0) -> IgemmArgs:
+    """What the tensors and the geometry give of a pmi_igemm call of m rows through `lin` (shapes, pitches, pointers, types): no library query, no
+    routing field.  c0 / c1: channels of a0 / a1 as the kernel counts them; grid = (H, W, Hin, Win).  Without tensors: a plain GEMM on dense rows of lin's
+    own K, the probe geglu_linear and fused_mlp_epilogues ask about.  (Fields that stay zero are not written: this runs for every launch.)"""
+    a = IgemmArgs()
+    a.M, a.N, a.K, a.ldb, a.hw, a.batch, a.batch_inner, a.dtype = m, lin.n_p, lin.K, lin.K, hw, 1, 1, lin.dt
+    a.taps, a.stride, a.alpha = lin.taps, stride, alpha
+    if up or res_up or act:
+        a.up, a.res_up, a.act = int(up), int(res_up), act
+    if lin.split or split_out:
+        a.split_in, a.split_out = int(lin.split), split_out
+    if grid is not None:
+        a.H, a.W, a.Hin, a.Win = grid
+    if a0 is not None:
+        a.A0, a.C0, a.lda0, a.B, a.bias = ptr(a0), c0, a0.stride(-2), ptr(lin.w), ptr(lin.b)
+    else:
+        a.C0, a.lda0 = lin.K, lin.K
+    if a1 is not None:
+        a.A1, a.C1, a.lda1 = ptr(a1), c1, a1.stride(-2)
+    if out is not None:
+        a.D, a.ldd = ptr(out), out.stride(-2)
+        if out.dtype is torch.float32:
+            a.out_f32 = 1
+    else:
+        a.ldd = lin.n_p
+    if residual is not None:
+        a.R, a.ldr = ptr(residual), residual.stride(-2)
+        if residual.dtype is torch.float32:
+            a.res_f32 = 1
+    if nbias is not None:
+        a.nbias, a.ldnb = ptr(nbias), nbias.stride(0)
+    return a
+
+
+def _as_if(query, ref, *more, Bf=_MARK, **fields) -> int:
+    """query(ref, *more) as if fragment-ordered weights were offered (Bf) and `fields` were set -- the one place that writes markers: the library reads a
+    pointer of a query as "this operand will be there" (pro_a: a fused prologue, D2: a second output).  The struct comes back as it was found."""
+    a = ref._obj
+    old_bf, old = a.Bf, [getattr(a, f) for f in fields] if fields else ()
+    a.Bf = Bf
+    for f, v in fields.items():
+        setattr(a, f, v)
+    try:
+        return query(ref, *more)
+    finally:
+        a.Bf = old_bf
+        for f, v in zip(fields, old):
+            setattr(a, f, v)
+
+
+def _timed(name: str, args):          # one library call between two events on the launch stream: (e0, e1)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    call(name, *args)
+    e1.record()
+    return e0, e1
+
+
+def _traced_call(name: str, args, desc: str, flops: float) -> None:
+    """One library call between two events, appended to GEMM_TRACE as (desc, flops, ev0, ev1)."""
+    GEMM_TRACE.append((desc, flops) + _timed(name, args))
+
+
+def _launch(name: str, *args, events=None, trace=None) -> None:
+    """The one launch seam: events = (flops, bytes, desc): timed into KERNEL_EVENTS as (e0, e1, flops, bytes, desc); trace = (desc, flops): into GEMM_TRACE."""
+    if events is None and trace is None:
+        call(name, *args)
+    elif events is not None:
+        KERNEL_EVENTS.append(_timed(name, args) + events)
+    else:
+        _traced_call(name, args, *trace)
+
+
+def _stats_buffer(a: IgemmArgs, out: torch.Tensor, n: int, rows: int, cols: int) -> None:
+    if rows > 0:       # the launch leaves per-channel (sum, sumsq) partials of its output for the next GroupNorm, kept on the output as _pmi_stats
+        st = _empty((n, rows, cols, 2), torch.float32, out.device)
+        a.stats, a.stats_p = ptr(st), rows
+        out._pmi_stats = (st, rows)
 
 
 def conv3x3_mixed(x: torch.Tensor, mlin: MixedLinear, *, operand: str, prologue, x1: Optional[torch.Tensor] = None, up: bool = False,
@@ -356,21 +438,16 @@ def conv3x3_mixed(x: torch.Tensor, mlin: MixedLinear, *, operand: str, prologue,
     h, w = (hin * 2, win * 2) if up else (hin, win)
     ca, cb, pact = prologue
     lin = mlin.single if operand == "single" else mlin.dbl
-    a = IgemmArgs()
     div = 2 if operand == "single" else 1                  # single: C0 / C1 / K count logical channels
     c0, c1 = x.shape[-1] // div, (x1.shape[-1] // div if x1 is not None else 0)
-    a.H, a.W, a.Hin, a.Win, a.hw = h, w, hin, win, h * w
     m = n * h * w
-    a.M, a.N, a.K, a.C0, a.C1 = m, lin.n_p, lin.K, c0, c1
-    a.lda0, a.lda1 = x.stride(-2), (x1.stride(-2) if x1 is not None else 0)
-    a.taps, a.stride, a.up, a.res_up, a.act, a.alpha = 9, 1, int(up), int(res_up), ACT_NONE, 1.0
-    a.batch, a.batch_inner, a.dtype = 1, 1, DT_F16X2
-    a.split_in, a.split_out = (2 if operand == "single" else 1), 32
-    a.A0, a.A1, a.B, a.bias, a.nbias, a.R = ptr(x), ptr(x1), ptr(lin.w), ptr(lin.b), ptr(nbias), ptr(residual)
-    a.ldb, a.ldr, a.ldnb = lin.K, (residual.stride(-2) if residual is not None else 0), (nbias.stride(0) if nbias is not None else 0)
-    a.res_f32 = int(residual is not None and residual.dtype == torch.float32)     # an fp32 residual (the 1x1 skip_connection's output) costs the same bytes as a split one
-    a.pro_a, a.pro_b, a.pro_act, a.Bf = 1, 1, pact, 1      # markers for the config query
-    cfg = _hip.lib().pmi_conv3x3_halo_config(C.byref(a)) if (lin.n_p % 128 == 0 and lin.K == 9 * (c0 + c1) and WD_ENABLED and HALO_ENABLED) else -1
+    a = _igemm_args(lin, m, x, x1, c0, c1, residual=residual, nbias=nbias, grid=(h, w, hin, win), hw=h * w, up=up, res_up=res_up, split_out=32)
+    a.dtype, a.split_in = DT_F16X2, (2 if operand == "single" else 1)     # split tensors whatever the weights' type (an fp32 residual: the same bytes as a split one)
+    a.pro_act = pact
+    ref, lib = C.byref(a), _hip.lib()
+    cfg = -1
+    if lin.n_p % 128 == 0 and lin.K == 9 * (c0 + c1) and HALO_ENABLED:
+        cfg = _as_if(lib.pmi_conv3x3_halo_config, ref, pro_a=_MARK, pro_b=_MARK)
     if MIXED_TRACE is not None:
         MIXED_TRACE.append(("wd" if cfg >= 6 else "fallback", operand, (n, h, w, c0 + c1, lin.cout)))
     if cfg < 6:
@@ -381,26 +458,18 @@ def conv3x3_mixed(x: torch.Tensor, mlin: MixedLinear, *, operand: str, prologue,
         return igemm(x, mlin.dbl, a1=x1, up=up, residual=residual, res_up=res_up, nbias=nbias, prologue=prologue, want_stats=True)
     ck = 64 if cfg == 6 else 32
     a.Bf = ptr(lin.frag16(ck) if operand == "single" else lin.frag16(ck, dup_g=ck // 2))
-    a.pro_a, a.pro_b, a.pro_act = ptr(ca), ptr(cb), pact
+    a.pro_a, a.pro_b = ptr(ca), ptr(cb)
     out = _empty((n, h, w, 2 * lin.n_p), torch.float16, x.device)
     a.D, a.ldd = ptr(out), out.stride(-2)
-    rows = _hip.lib().pmi_igemm_stats_rows(C.byref(a))
-    if rows > 0:
-        st = _empty((n, rows, lin.n_p, 2), torch.float32, x.device)
-        a.stats, a.stats_p = ptr(st), rows
-        out._pmi_stats = (st, rows)
+    _stats_buffer(a, out, n, lib.pmi_igemm_stats_rows(ref), lin.n_p)
     if DEBUG_WS is not None:
         a.ws = ptr(DEBUG_WS)
         a.reserved = 77
+    events = None
     if KERNEL_EVENTS is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call("pmi_igemm", C.byref(a))
-        e1.record()
         nbytes = (x.numel() + (x1.numel() if x1 is not None else 0)) * 2 + lin.w.numel() * 2 + out.numel() * 2 + (residual.numel() * 2 if residual is not None else 0)
-        KERNEL_EVENTS.append((e0, e1, 2.0 * m * lin.cout * lin.cin * 9, float(nbytes), f"{h}x{w} {c0}+{c1}->{lin.cout} cfg{cfg} mixed-{operand}"))
-        return out
-    call("pmi_igemm", C.byref(a))
+        events = (2.0 * m * lin.cout * lin.cin * 9, float(nbytes), f"{h}x{w} {c0}+{c1}->{lin.cout} cfg{cfg} mixed-{operand}")
+    _launch("pmi_igemm", ref, events=events)
     return out
 
 
@@ -411,13 +480,8 @@ def _wd_tile_desc(a: IgemmArgs) -> str:
     return f" rows={t // 1000} cols={t % 1000}{' two' if a.A1 else ''}{' convmode' if a.taps == 9 else ''}{' geglu' if a.act == ACT_GEGLU else ''}"
 
 
-def _traced_call(name: str, args, desc: str, flops: float) -> None:
-    """One library call between two events, appended to GEMM_TRACE as (desc, flops, ev0, ev1)."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    call(name, *args)
-    e1.record()
-    GEMM_TRACE.append((desc, flops, e0, e1))
+_CONV_PACKING = {4: lambda lin: lin.frag(64), 6: lambda lin: lin.frag16(64), 7: lambda lin: lin.frag16(32), 8: lambda lin: lin.frag_c8(),
+                 9: lambda lin: lin.frag16_up(64)}     # the weight order each weights-direct 3x3 tile config reads through Bf (the others: lin.w)
 
 
 def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
@@ -436,99 +500,79 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
     (LDS-halo conv3x3 kernel only); when the shape is not eligible the apply kernel runs first.
     pre_out: 16-bit tensor like the output that receives the PRE-activation value (fused act epilogue keeps the backward's input);
     act_grad_of / act_grad: the output is multiplied by act'(act_grad_of) -- both only where fused_mlp_epilogues(lin) is True."""
-    dt = lin.dt
-    conv = a0.ndim == 4
+    # ---- 1. geometry and arguments: no library query ----
+    dt, conv = lin.dt, a0.ndim == 4
     if lin.concat_inputs and a1 is not None and prologue is None:
         # (a prologue materialises one applied tensor from both sources below: no copy needed there)
         a0, a1 = torch.cat([a0, a1], dim=-1), None
-    c0 = a0.shape[-1]
-    c1 = a1.shape[-1] if a1 is not None else 0
+    c0, c1 = a0.shape[-1], (a1.shape[-1] if a1 is not None else 0)
     assert (c0 + c1) * (2 if lin.self_concat else 1) == lin.cin_p, (c0, c1, lin.cin_p)
-    a = IgemmArgs()
     if conv:
         n, hin, win, _ = a0.shape
         hv, wv = (hin * 2, win * 2) if up else (hin, win)
         h, w = hv // stride, wv // stride
-        m = n * h * w
-        a.H, a.W, a.Hin, a.Win = h, w, hin, win
-        a.hw = h * w
+        m, grid, hw = n * h * w, (h, w, hin, win), h * w
         oshape = (n, h, w, lin.n_p)
     else:
         assert lin.taps == 1 and not up and stride == 1
-        m = a0.shape[0]
-        a.hw = hw or 1
+        m, grid, hw = a0.shape[0], None, hw or 1
         oshape = (m, lin.n_p // 2 if act == ACT_GEGLU else lin.n_p)
-    if lin.split:
-        a.split_in = 1
-    if (lin.split and not out_f32) or split_out:          # precise output: hi + lo pairs, 2*N 16-bit values per row (split_out: from plain f16
-        a.split_out = split_group(lin.n_p)                # operands too -- the mixed mode's attention projection back onto a split stream)
-        oshape = oshape[:-1] + (2 * lin.n_p,)
+    so = split_group(lin.n_p) if (lin.split and not out_f32) or split_out else 0
+    if so:     # precise output: hi + lo pairs, 2*N 16-bit values per row (split_out: from plain f16 operands too -- the mixed mode's attention
+        oshape = oshape[:-1] + (2 * lin.n_p,)             # projection back onto a split stream)
     if out is None:
         out = _empty(oshape, torch.float32 if out_f32 else _hip.TORCH_DTYPE[dt], a0.device)
-    a.A0, a.A1, a.B = ptr(a0), ptr(a1), ptr(lin.w)
-    a.bias, a.nbias, a.R, a.D = ptr(lin.b), ptr(nbias), ptr(residual), ptr(out)
-    a.M, a.N, a.K = m, lin.n_p, lin.K
-    a.C0, a.C1 = c0, c1
-    a.lda0, a.lda1 = a0.stride(-2), (a1.stride(-2) if a1 is not None else 0)
-    a.ldb, a.ldd = lin.K, out.stride(-2)
-    a.ldr = residual.stride(-2) if residual is not None else 0
-    a.taps, a.stride, a.up, a.res_up, a.act = lin.taps, stride, int(up), int(res_up), act
-    a.out_f32 = int(out.dtype == torch.float32)
-    a.res_f32 = int(residual is not None and residual.dtype == torch.float32)
-    a.alpha = alpha
-    a.ldnb = nbias.stride(0) if nbias is not None else 0
-    a.batch, a.batch_inner = 1, 1
-    a.dtype = dt
-    cfg = -1
-    if conv and lin.taps == 9 and stride == 1 and HALO_ENABLED and WD_ENABLED and lin.n_p % 32 == 0 and ((lin.n_p >= 128 and lin.cin_p % 64 == 0) or (lin.cin_p <= 32 and a1 is None)):
-        a.Bf = 1                       # ask which tile config the weights-direct kernel would run, then hand it that packing
-        a.pro_a = 1 if (prologue is not None and not lin.split) else None     # (the table size limit depends on a fused prologue)
-        if up and lin.frag16_up(64) is None:
-            a.reserved3 = 2            # no phase weights: the up-sampling convolution stays on the gather route (config 9 needs them)
-        cfg = _hip.lib().pmi_conv3x3_halo_config(C.byref(a))
-        a.pro_a = None
-        a.Bf = ptr(lin.frag16_up(64)) if cfg == 9 else ptr(lin.frag16(64)) if cfg == 6 else ptr(lin.frag16(32)) if cfg == 7 else ptr(lin.frag(64)) if cfg == 4 else ptr(lin.frag_c8()) if cfg == 8 else None
+    a = _igemm_args(lin, m, a0, a1, c0, c1, out=out, residual=residual, nbias=nbias, grid=grid, hw=hw, stride=stride, up=up, res_up=res_up, act=act,
+                    alpha=alpha, split_out=so)
     if pre_out is not None or act_grad_of is not None:
         a.D2, a.aux, a.aux_act = ptr(pre_out), ptr(act_grad_of), act_grad
-    # (split weights: their duplicated K is an ordinary K for the weights-direct GEMM; its epilogues write plain 16-bit or fp32 rows only)
-    wd_ok = GEMM_WD_ENABLED and lin.taps == 1 and (not lin.split or out_f32) and not up and stride == 1 and lin.n_p % 32 == 0 and lin.K % 32 == 0 \
+    ref, lib, packed, cfg = C.byref(a), _hip.lib(), False, -1          # packed: Bf holds a weight order (steps 2, 3, 4, 7)
+    # ---- 2. 3x3 tile config and its packing, asked BEFORE the steps below change the struct: pmi_igemm chooses again from the struct as launched (DESIGN.md 4.2.1) ----
+    if conv and lin.taps == 9 and stride == 1 and HALO_ENABLED and lin.n_p % 32 == 0 and ((lin.n_p >= 128 and lin.cin_p % 64 == 0) or (lin.cin_p <= 32 and a1 is None)):
+        if up and lin.frag16_up(64) is None:
+            a.reserved3 = 2            # no phase weights: the up-sampling convolution stays on the gather route (config 9 needs them); stays set for the launch
+        if prologue is not None and not lin.split:         # (the table size limit depends on a fused prologue)
+            cfg = _as_if(lib.pmi_conv3x3_halo_config, ref, pro_a=_MARK)
+        else:
+            cfg = _as_if(lib.pmi_conv3x3_halo_config, ref)
+        if cfg in _CONV_PACKING:
+            a.Bf, packed = ptr(_CONV_PACKING[cfg](lin)), True
+    # ---- 3. weights-direct GEMM (csrc/gemm_wd.hip) for a plain GEMM (split weights: their duplicated K is an ordinary K; its epilogues write plain 16-bit or fp32 rows only) ----
+    wd = GEMM_WD_ENABLED and lin.taps == 1 and (not lin.split or out_f32) and not up and stride == 1 and lin.n_p % 32 == 0 and lin.K % 32 == 0 \
         and nbias is None and prologue is None
-    if wd_ok and want_stats:
+    if wd and want_stats:
         # the weights-direct GEMM has no statistics epilogue; the generic kernel has none either once it splits K (attention proj_out on
         # 16x16 / 8x8 maps): then the faster GEMM runs and the consumer's GroupNorm takes its statistics pass as before
-        wd_ok = SPLITK_ENABLED and _hip.lib().pmi_igemm_splitk(C.byref(a)) > 1
-    if wd_ok:
-        a.Bf = 1                               # plain GEMM: ask whether the weights-direct kernel (csrc/gemm_wd.hip) takes this shape ...
-        a.Bf = ptr(lin.frag_gemm()) if _hip.lib().pmi_gemm_wd_eligible(C.byref(a)) else None      # ... and only then pack its weight order
-        if a.Bf:
-            want_stats = False
-    fused_skip, k = False, None
+        wd = SPLITK_ENABLED and lib.pmi_igemm_splitk(ref) > 1          # (asked without Bf: the GENERIC kernel's split rule)
+    if wd:                                     # ask whether the kernel takes this shape, and only then pack its weight order
+        wd = bool(_as_if(lib.pmi_gemm_wd_eligible, ref))
+        if wd:
+            a.Bf, packed, want_stats = ptr(lin.frag_gemm()), True, False
+    # ---- 4. a ResBlock's skip convolution: inside this launch (pmi_conv3x3_skip), or its own GEMM whose output is the residual ----
+    fcfg = 0
     if skip is not None:
         slin, s0, s1, sbias = skip
         assert residual is None and conv and prologue is not None
-        if act == ACT_NONE and a1 is None and HALO_ENABLED and WD_ENABLED and not lin.split and not slin.split and slin.taps == 1 and slin.n_p == lin.n_p \
+        if act == ACT_NONE and a1 is None and HALO_ENABLED and not lin.split and not slin.split and slin.taps == 1 and slin.n_p == lin.n_p \
                 and lin.n_p % 128 == 0 and lin.cin_p % 64 == 0 and slin.K % 64 == 0:
             k = SkipArgs()
             k.X0, k.X1, k.Wf = ptr(s0), ptr(s1), ptr(slin.frag_skip())
             k.C0, k.C1 = s0.shape[-1], (s1.shape[-1] if s1 is not None else 0)
             k.ld0, k.ld1 = s0.stride(-2), (s1.stride(-2) if s1 is not None else 0)
-            keep = (a.Bf, a.bias)
-            a.Bf = ptr(lin.w)   # (any pointer: the query names the tile config, a function of the layer and the map alone, and Bf follows it)
-            a.bias = ptr(sbias)
-            a.pro_a, a.pro_b, a.pro_act = ptr(prologue[0]), ptr(prologue[1]), prologue[2]
-            fcfg = _hip.lib().pmi_conv3x3_skip_eligible(C.byref(a), C.byref(k))
-            fused_skip = fcfg in (6, 7)
-            if fused_skip:
-                a.Bf = ptr(lin.frag16(64 if fcfg == 6 else 32))
-            else:
-                a.Bf, a.bias = keep
-                a.pro_a, a.pro_b, a.pro_act = None, None, 0
-        if not fused_skip:
+            fcfg = _as_if(lib.pmi_conv3x3_skip_eligible, ref, C.byref(k), Bf=ptr(lin.w), bias=ptr(sbias), pro_a=ptr(prologue[0]),
+                          pro_b=ptr(prologue[1]), pro_act=prologue[2])     # (Bf: any 16-byte aligned pointer; the config names the packing)
+        if fcfg in (6, 7):
+            a.Bf, a.bias, packed = ptr(lin.frag16(64 if fcfg == 6 else 32)), ptr(sbias), True
+        else:
             residual = igemm(s0, slin, a1=s1)
             a.R, a.ldr, a.res_f32 = ptr(residual), residual.stride(-2), 0
-    if prologue is not None and not fused_skip:
+    fused_skip = fcfg in (6, 7)
+    # ---- 5. prologue: fused where a 3x3 tile config takes the struct as it stands (Bf from step 2, no pro_a marker), else the apply pass ----
+    fused_pro = False
+    if prologue is not None:
         ca, cb, pact = prologue
-        if HALO_ENABLED and not lin.split and _hip.lib().pmi_conv3x3_halo_config(C.byref(a)) >= 0:
+        fused_pro = fused_skip or (HALO_ENABLED and not lin.split and lib.pmi_conv3x3_halo_config(ref) >= 0)
+        if fused_pro:
             a.pro_a, a.pro_b, a.pro_act = ptr(ca), ptr(cb), pact
         else:   # not eligible: materialise act(x*a+b) with the streaming kernel, then convolve
             if lin.split and a1 is not None and (c0 // 2) % 32 + (c1 // 2) % 32:
@@ -541,82 +585,68 @@ def igemm(a0: torch.Tensor, lin: PackedLinear, *, a1: Optional[torch.Tensor] = N
             call("pmi_gn_apply", ptr(a0), ptr(a1), lc0, ptr(ca), ptr(cb), None, ptr(y), n_, h_, w_, lc, pact, 0, dt)
             a.A0, a.A1, a.C0, a.C1, a.lda0, a.lda1 = ptr(y), None, c0 + c1, 0, c0 + c1, 0
             a0 = y
-    if lin.self_concat:        # precise mode, fp32 weights: their low part multiplies the SAME input again as a second source
+    # ---- 6. self_concat (precise mode, fp32 weights): their low part multiplies the SAME input again as a second source ----
+    if lin.self_concat:
         assert a.A1 is None
         a.A1, a.C1, a.lda1 = a.A0, a.C0, a.lda0
+    # ---- 7. a 3x3 convolution the conv3x3 kernels do not take (16x16 / 8x8 maps): the weights-direct GEMM's conv mode, if it does ----
     conv_gemm = False
-    if conv and lin.taps == 9 and stride == 1 and not up and GEMM_WD_ENABLED and GEMM_WD_CONV and not lin.split and not a.Bf \
-            and not a.pro_a and lin.n_p % 32 == 0 and c0 % 128 == 0 and c1 % 128 == 0:
-        a.Bf = 1           # a 3x3 convolution the conv3x3 kernels do not take (16x16 / 8x8 maps): the weights-direct GEMM's conv mode, if it does
-        a.Bf = ptr(lin.frag_gemm()) if _hip.lib().pmi_gemm_wd_eligible(C.byref(a)) else None
-        conv_gemm = bool(a.Bf)
+    if conv and lin.taps == 9 and stride == 1 and not up and GEMM_WD_ENABLED and GEMM_WD_CONV and not lin.split and not packed \
+            and not fused_pro and lin.n_p % 32 == 0 and c0 % 128 == 0 and c1 % 128 == 0:
+        conv_gemm = bool(_as_if(lib.pmi_gemm_wd_eligible, ref))
+        if conv_gemm:
+            a.Bf = ptr(lin.frag_gemm())
+    # ---- 8. split-K: few output tiles, long K -- the reduction over grid.z into fp32 slabs (asked with the Bf of steps 2 / 3 / 7) ----
+    sk = 0
     if SPLITK_ENABLED and not fused_skip:
-        sk = _hip.lib().pmi_igemm_splitk(C.byref(a))
-        if sk > 1:   # few output tiles, long K: split the reduction over grid.z into fp32 slabs
+        sk = lib.pmi_igemm_splitk(ref)
+        if sk > 1:
             ws = _empty((sk, m, lin.n_p), torch.float32, a0.device)
             a.ws, a.splitk = ptr(ws), sk
-            if defer_reduce and a.Bf and not conv and _hip.lib().pmi_gemm_wd_eligible(C.byref(a)):
+            if defer_reduce and packed and not conv and lib.pmi_gemm_wd_eligible(ref):
                 # the caller fuses the reduction (+ bias / residual) into its next pass (LayerNorm): leave the raw slabs
                 a.reserved3 = 1
-                if GEMM_TRACE is not None:
-                    _traced_call("pmi_igemm", (C.byref(a),), f"gemm M={m} N={lin.n_p} K={lin.K} taps=1 splitk={sk} halo=-1 wd=1{_wd_tile_desc(a)} defer",
-                                 2.0 * m * lin.n_p * lin.K)
-                    return ("slabs", ws, sk)
-                call("pmi_igemm", C.byref(a))
+                _launch("pmi_igemm", ref, trace=None if GEMM_TRACE is None else
+                        (f"gemm M={m} N={lin.n_p} K={lin.K} taps=1 splitk={sk} halo=-1 wd=1{_wd_tile_desc(a)} defer", 2.0 * m * lin.n_p * lin.K))
                 return ("slabs", ws, sk)
-    if conv_gemm and (nbias is not None or res_up) and a.splitk <= 1:
-        a.Bf = None            # a per-sample bias / up-sampled residual is the split-K reduce kernel's: unsplit, the generic kernel takes the call
+    if conv_gemm and (nbias is not None or res_up) and sk <= 1:
+        a.Bf, conv_gemm = None, False      # a per-sample bias / up-sampled residual is the split-K reduce kernel's: unsplit, the generic kernel takes the call (sk: asked with Bf set)
+    # ---- 9. statistics: fused per-channel (sum, sumsq) of the output for the next GroupNorm ----
     if want_stats:
-        rows = (a.H // 8) * (a.W // 32) if fused_skip else _hip.lib().pmi_igemm_stats_rows(C.byref(a))
-        if rows > 0:   # fused per-channel (sum, sumsq) of the output for the next GroupNorm
-            st = _empty((m // a.hw, rows, lin.n_p, 2), torch.float32, a0.device)
-            a.stats, a.stats_p = ptr(st), rows
-            out._pmi_stats = (st, rows)
-    if DEBUG_WS is not None and a.splitk <= 1:      # (a split-K call's ws is its slab workspace: the phase stamps of the probes are for unsplit calls only)
+        _stats_buffer(a, out, m // hw, (h // 8) * (w // 32) if fused_skip else lib.pmi_igemm_stats_rows(ref), lin.n_p)
+    if DEBUG_WS is not None and sk <= 1:      # (a split-K call's ws is its slab workspace: the phase stamps of the probes are for unsplit calls only)
         a.ws = ptr(DEBUG_WS)
         a.reserved = 77
+    # ---- 10. launch; instrumented: a 3x3 launch on a tile config goes to KERNEL_EVENTS when that is on, otherwise to GEMM_TRACE ----
+    events = trace = None
+    if KERNEL_EVENTS is not None or GEMM_TRACE is not None:
+        # what pmi_igemm itself computes from the struct as launched is what is printed: its tile config here, its weights-direct GEMM test below
+        tile = fcfg if fused_skip else lib.pmi_conv3x3_halo_config(ref) if (HALO_ENABLED and lin.taps == 9) else -1
+        if KERNEL_EVENTS is not None and tile >= 0:
+            # algorithmic HBM bytes: input read once, packed weights, output written once, residual read once; a fused skip adds its product's FLOP, its two sources and its weights
+            nbytes = (a0.numel() + (a1.numel() if a1 is not None else 0)) * 2 + lin.w.numel() * 2 + out.numel() * out.element_size() \
+                + (residual.numel() * residual.element_size() if residual is not None else 0)
+            if fused_skip:
+                nbytes += (s0.numel() + (s1.numel() if s1 is not None else 0)) * 2 + slin.w.numel() * 2
+            desc = f"{h}x{w} {c0}+{c1}->{lin.cout} cfg{tile}{' pro' if prologue is not None else ''}{' res' if residual is not None else ''}" \
+                   f"{' up' if up else ''}{f' skip {k.C0}+{k.C1}' if fused_skip else ''}{' stats' if want_stats else ''}"
+            events = (2.0 * m * lin.cout * (lin.cin * lin.taps + (slin.cin if fused_skip else 0)), float(nbytes), desc)
+        elif GEMM_TRACE is not None and fused_skip:
+            trace = (f"conv M={m} N={lin.n_p} K={lin.K} taps=9 splitk=0 halo={tile} wd=0{' stats' if a.stats else ''} skip={k.C0}+{k.C1}",
+                     2.0 * m * lin.n_p * (lin.K + slin.K))
+        elif GEMM_TRACE is not None:
+            kind = "conv" if conv and (lin.taps == 9 or up or stride == 2) else "gemm"
+            # (not the locals of steps 3 / 7: statistics attached in step 9 make pmi_igemm refuse the weights-direct GEMM and ignore Bf)
+            wd = bool(a.Bf) and bool(lib.pmi_gemm_wd_eligible(ref))
+            desc = f"{kind} M={m} N={lin.n_p} K={lin.K} taps={lin.taps}{' up' if up else ''}{' s2' if stride == 2 else ''} splitk={a.splitk} halo={tile} wd={int(wd)}" \
+                   f"{' res' if residual is not None else ''}{' f32out' if a.out_f32 else ''}{' nbias' if nbias is not None else ''}{' stats' if a.stats else ''}" \
+                   f"{' split_in' if a.split_in else ''}{' split_out' if a.split_out else ''}{' self_concat' if lin.self_concat else ''}" \
+                   f"{_wd_tile_desc(a) if wd else ''}"
+            trace = (desc, 2.0 * m * lin.n_p * lin.K)
     if fused_skip:
-        if KERNEL_EVENTS is None:
-            if GEMM_TRACE is not None:
-                _traced_call("pmi_conv3x3_skip", (C.byref(a), C.byref(k)),
-                             f"conv M={m} N={lin.n_p} K={lin.K} taps=9 splitk=0 halo={fcfg} wd=0{' stats' if a.stats else ''} skip={k.C0}+{k.C1}",
-                             2.0 * m * lin.n_p * (lin.K + slin.K))
-                return out
-            call("pmi_conv3x3_skip", C.byref(a), C.byref(k))
-            return out
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call("pmi_conv3x3_skip", C.byref(a), C.byref(k))
-        e1.record()
-        # the plain launch's figures plus the skip product's: 2 M cin cout FLOP, its two sources and its weights read once
-        nbytes = a0.numel() * 2 + lin.w.numel() * 2 + out.numel() * out.element_size() + (s0.numel() + (s1.numel() if s1 is not None else 0)) * 2 + slin.w.numel() * 2
-        desc = f"{a.H}x{a.W} {c0}+{c1}->{lin.cout} cfg{fcfg} pro skip {k.C0}+{k.C1}{' stats' if want_stats else ''}"
-        KERNEL_EVENTS.append((e0, e1, 2.0 * m * lin.cout * (lin.cin * lin.taps + slin.cin), float(nbytes), desc))
-        return out
-    if KERNEL_EVENTS is not None and lin.taps == 9 and HALO_ENABLED and _hip.lib().pmi_conv3x3_halo_config(C.byref(a)) >= 0:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call("pmi_igemm", C.byref(a))
-        e1.record()
-        # algorithmic HBM bytes of the launch: input read once, packed weights, output written once, residual read once
-        nbytes = (a0.numel() + (a1.numel() if a1 is not None else 0)) * 2 + lin.w.numel() * 2 + out.numel() * out.element_size()
-        if residual is not None:
-            nbytes += (residual.numel() if not res_up else residual.numel()) * residual.element_size()
-        desc = f"{a.H}x{a.W} {c0}+{c1}->{lin.cout} cfg{_hip.lib().pmi_conv3x3_halo_config(C.byref(a))}" \
-               f"{' pro' if prologue is not None else ''}{' res' if residual is not None else ''}{' up' if up else ''}{' stats' if want_stats else ''}"
-        KERNEL_EVENTS.append((e0, e1, 2.0 * m * lin.cout * lin.cin * lin.taps, float(nbytes), desc))
-        return out
-    if GEMM_TRACE is not None:
-        kind = "conv" if conv and (lin.taps == 9 or up or stride == 2) else "gemm"
-        wd = bool(a.Bf) and bool(_hip.lib().pmi_gemm_wd_eligible(C.byref(a)))
-        desc = f"{kind} M={m} N={lin.n_p} K={lin.K} taps={lin.taps}{' up' if up else ''}{' s2' if stride == 2 else ''} splitk={a.splitk}" \
-               f" halo={_hip.lib().pmi_conv3x3_halo_config(C.byref(a)) if HALO_ENABLED else -1} wd={int(wd)}" \
-               f"{' res' if residual is not None else ''}{' f32out' if a.out_f32 else ''}{' nbias' if nbias is not None else ''}{' stats' if a.stats else ''}" \
-               f"{' split_in' if a.split_in else ''}{' split_out' if a.split_out else ''}{' self_concat' if lin.self_concat else ''}" \
-               f"{_wd_tile_desc(a) if wd else ''}"
-        _traced_call("pmi_igemm", (C.byref(a),), desc, 2.0 * m * lin.n_p * lin.K)
-        return out
-    call("pmi_igemm", C.byref(a))
+        _launch("pmi_conv3x3_skip", ref, C.byref(k), events=events, trace=trace)
+    else:
+        _launch("pmi_igemm", ref, events=events, trace=trace)
     return out
 
 
@@ -624,16 +654,8 @@ def downsample_adjoint_args(g: torch.Tensor, lin: PackedLinear, out: torch.Tenso
     """pmi_igemm's phased geometry (taps 9, stride 2, up 2) for g [N, h, w, C] -> out [N, 2h, 2w, C']: H x W is the output grid, Hin x Win the
     gradient's, M counts output pixels (a quarter of them per phase)."""
     n, h, w, c = g.shape
-    a = IgemmArgs()
-    a.A0, a.B, a.D = ptr(g), ptr(lin.w), ptr(out)
-    a.M, a.N, a.K = 4 * n * h * w, lin.n_p, lin.K
-    a.C0, a.lda0, a.ldb, a.ldd = c, g.stride(-2), lin.K, out.stride(-2)
-    a.H, a.W, a.Hin, a.Win, a.hw = 2 * h, 2 * w, h, w, 4 * h * w
-    a.taps, a.stride, a.up = 9, 2, 2
-    a.out_f32 = int(out.dtype == torch.float32)
-    a.alpha = 1.0
-    a.batch, a.batch_inner = 1, 1
-    a.dtype = lin.dt
+    a = _igemm_args(lin, 4 * n * h * w, g, None, c, out=out, grid=(2 * h, 2 * w, h, w), hw=4 * h * w, stride=2, up=2)
+    a.bias = None          # (a gradient takes no bias)
     return a
 
 
@@ -653,14 +675,12 @@ def downsample_adjoint(g: torch.Tensor, lin: PackedLinear, *, out_f32: bool = Fa
 def geglu_linear(x: torch.Tensor, lin: PackedLinear) -> torch.Tensor:
     """x [M, K] @ lin (columns packed as 16 value | 16 gate per 32: interleave_geglu) -> value * gelu(gate) [M, N / 2].
     In the GEMM's epilogue where the weights-direct kernel takes the shape; otherwise the GEMM followed by the gate pass."""
-    dt = lin.dt
-    a = IgemmArgs()
-    a.taps, a.stride, a.M, a.N, a.K, a.C0, a.batch, a.Bf, a.act = 1, 1, x.shape[0], lin.n_p, lin.K, lin.K, 1, 1, ACT_GEGLU
-    if GEMM_WD_ENABLED and not lin.split and lin.n_p % 32 == 0 and lin.K % 32 == 0 and _hip.lib().pmi_gemm_wd_eligible(C.byref(a)):
+    if GEMM_WD_ENABLED and not lin.split and lin.n_p % 32 == 0 and lin.K % 32 == 0 \
+            and _as_if(_hip.lib().pmi_gemm_wd_eligible, C.byref(_igemm_args(lin, x.shape[0], act=ACT_GEGLU))):
         return igemm(x, lin, act=ACT_GEGLU)
     f = igemm(x, lin)
     out = _empty((x.shape[0], lin.n_p // 2), f.dtype, f.device)
-    call("pmi_geglu", ptr(f), ptr(out), x.shape[0], lin.n_p // 2, 1, dt)
+    call("pmi_geglu", ptr(f), ptr(out), x.shape[0], lin.n_p // 2, 1, lin.dt)
     return out
 
 
@@ -682,13 +702,10 @@ def fused_mlp_epilogues(lin: PackedLinear, m: int) -> bool:
     # reproduce its slice of the full-batch gradient, tests/test_gpu_clip.py): wide layers only, any m a ViT batch produces
     if not (GEMM_WD_ENABLED and lin.taps == 1 and not lin.split and lin.n_p % 256 == 0 and lin.K % 128 == 0 and m >= 64):
         return False
-    a = IgemmArgs()
-    a.taps, a.stride, a.M, a.N, a.K, a.C0, a.batch, a.batch_inner, a.hw = 1, 1, m, lin.n_p, lin.K, lin.K, 1, 1, 1
-    a.lda0, a.ldb, a.ldd, a.dtype, a.alpha = lin.K, lin.K, lin.n_p, lin.dt, 1.0
-    a.Bf, a.D2 = 1, 1                        # non-null markers: eligibility is asked for a call WITH the second output
-    if SPLITK_ENABLED and _hip.lib().pmi_igemm_splitk(C.byref(a)) > 1:
+    ref, lib = C.byref(_igemm_args(lin, m)), _hip.lib()
+    if SPLITK_ENABLED and _as_if(lib.pmi_igemm_splitk, ref, D2=_MARK) > 1:       # (D2: asked for a call WITH the second output)
         return False
-    return bool(_hip.lib().pmi_gemm_wd_eligible(C.byref(a)))
+    return bool(_as_if(lib.pmi_gemm_wd_eligible, ref, D2=_MARK))
 
 
 def bgemm(A: torch.Tensor, B: torch.Tensor, D: torch.Tensor, *, M: int, N: int, K: int, lda: int, ldb: int, ldd: int,
@@ -699,7 +716,7 @@ def bgemm(A: torch.Tensor, B: torch.Tensor, D: torch.Tensor, *, M: int, N: int, 
     a.A0 = A.data_ptr() + a_off * es
     a.B = B.data_ptr() + b_off * B.element_size()
     a.D = D.data_ptr() + d_off * D.element_size()
-    a.M, a.N, a.K, a.C0, a.C1 = M, N, K, K, 0
+    a.M, a.N, a.K, a.C0 = M, N, K, K
     a.lda0, a.ldb, a.ldd = lda, ldb, ldd
     a.taps, a.stride, a.hw, a.alpha = 1, 1, 1, alpha
     a.out_f32 = int(D.dtype == torch.float32)
@@ -708,14 +725,7 @@ def bgemm(A: torch.Tensor, B: torch.Tensor, D: torch.Tensor, *, M: int, N: int, 
     a.sB_o, a.sB_i = sB
     a.sD_o, a.sD_i = sD
     a.dtype = dt
-    if GEMM_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call("pmi_igemm", C.byref(a))
-        e1.record()
-        GEMM_TRACE.append((f"bgemm M={M} N={N} K={K} batch={batch}", 2.0 * M * N * K * batch, e0, e1))
-        return D
-    call("pmi_igemm", C.byref(a))
+    _launch("pmi_igemm", C.byref(a), trace=None if GEMM_TRACE is None else (f"bgemm M={M} N={N} K={K} batch={batch}", 2.0 * M * N * K * batch))
     return D
 
 
