@@ -451,6 +451,28 @@ int pmi_smoothness(const float* x, float* loss, float* grad, float* partial, int
 int pmi_sqdiff_loss(const float* a, const float* b, float* loss, float* g, float* partial, int64_t count, int64_t n_total_count,
                     pmi_stream_t s);
 
+/* ---- VGG-19 feature tower and the style-transfer loss (csrc/vgg.hip; perceptor/losses/style_transfer.py), 16-bit NHWC, dtype 0 / 1,
+ * fp32 accumulation, no atomics (results are bit-identical from run to run).  Convolutions + bias + ReLU and their input gradients
+ * are pmi_igemm, the ReLU masks pmi_act_bwd.
+ * pmi_maxpool2: nn.MaxPool2d(2, 2), x [N][H][W][C] -> y [N][H/2][W/2][C]; H, W even, C % 8 == 0.
+ * pmi_maxpool2_bwd: dx = route(dy) * (x > 0): each window's dy goes to its FIRST maximum in the order (0,0), (0,1), (1,0), (1,1)
+ *   (PyTorch's rule), recomputed from x (no index tensor); x is a post-ReLU activation, whose mask is applied in the same pass.
+ * pmi_gram: G[(n,c)][(m,d)] = scale * sum_p f[n][p][c] f[m][p][d], fp32 [N C][N C], exactly symmetric; C % 16 == 0, N C <= 8192, any
+ *   HW >= 1; ws = pmi_gram_workspace(N, HW, C) floats (split-K slabs, added in slab order).
+ * pmi_style_level: loss2[0] = mean |fa - fb| over N HW C values, loss2[1] = mean |Ga - Gb| over (N C)^2, S [N C][N C] 16-bit =
+ *   sign(Ga - Gb) in {-1, 0, +1}; partial = 2048 floats.
+ * pmi_gram_bwd: dF[n][p][c] = (fa > 0) * ( gscale * ( c_feat * sign(fa - fb)[n][p][c] + c_gram * sum_{m,d} (S + S^T)[(n,c)][(m,d)]
+ *   fa[m][p][d] ) + g_in[n][p][c] ), g_in nullable (the gradient arriving from deeper layers, already scaled by gscale); T = workspace of
+ *   (N C)^2 16-bit values that receives S + S^T. */
+int pmi_maxpool2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_maxpool2_bwd(const void* dy, const void* x, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_gram_workspace(int N, int HW, int C);
+int pmi_gram(const void* f, float* G, float* ws, int N, int HW, int C, float scale, int dtype, pmi_stream_t s);
+int pmi_style_level(const void* fa, const void* fb, const float* Ga, const float* Gb, void* S, float* loss2, float* partial, int N, int HW,
+                    int C, int dtype, pmi_stream_t s);
+int pmi_gram_bwd(const void* fa, const void* fb, const void* S, void* T, const void* g_in, void* dF, int N, int HW, int C, float c_feat,
+                 float c_gram, float gscale, int dtype, pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,13 @@ _PROTOS = {
     "pmi_head_loss": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _F, _P],),
     "pmi_smoothness": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],),
     "pmi_sqdiff_loss": ([_P, _P, _P, _P, _P, _L, _L, _P],),
+    # VGG-19 tower and style-transfer loss (vgg.hip)
+    "pmi_maxpool2": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_maxpool2_bwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_gram_workspace": ([_I, _I, _I],),
+    "pmi_gram": ([_P, _P, _P, _I, _I, _I, _F, _I, _P],),
+    "pmi_style_level": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],),
+    "pmi_gram_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _P],),
 }
 
 

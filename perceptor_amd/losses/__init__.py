@@ -5,3 +5,4 @@ from .aesthetic import AestheticVisualAssessment, SimulacraAesthetic
 from .pixel import Resize, Smoothness
 from .spherical_distance import SphericalDistance
 from .shared_tower import tower_loss_and_grad
+from .style_transfer import StyleTransfer

@@ -5,3 +5,4 @@ from .velocity_diffusion import VelocityDiffusion
 from .stable_diffusion import StableDiffusion
 from .transformers_openai_clip import TransformersOpenAICLIP
 from .simulacra_aesthetic import SimulacraAesthetic
+from .vgg import VGG19
