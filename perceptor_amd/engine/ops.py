@@ -699,7 +699,9 @@ def fused_mlp_epilogues(lin: PackedLinear, m: int) -> bool:
     write the pre-activation value (pre_out) and multiply by an activation gradient (act_grad_of).  The library decides (its split-K cost
     model and A/B options included): pmi_igemm rejects D2 / aux on any other route."""
     # the structural part keeps the choice independent of the batch a rank holds (fused and unfused epilogues round differently: a shard must
-    # reproduce its slice of the full-batch gradient, tests/test_gpu_clip.py): wide layers only, any m a ViT batch produces
+    # reproduce its slice of the full-batch gradient, tests/test_gpu_clip.py): wide layers only, any m a ViT batch produces.  The m >= 64
+    # floor and the split-K query below still follow m: a shard that crosses either (widths 512 / 768, m = 68 -> 34 in
+    # tests/test_gpu_vit_tower.py) equals its slice to 16-bit rounding, not bit for bit
     if not (GEMM_WD_ENABLED and lin.taps == 1 and not lin.split and lin.n_p % 256 == 0 and lin.K % 128 == 0 and m >= 64):
         return False
     ref, lib = C.byref(_igemm_args(lin, m)), _hip.lib()

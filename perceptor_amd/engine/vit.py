@@ -14,7 +14,7 @@ ln_post, proj.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -262,8 +262,11 @@ class VitEngine:
 
     # ---- input gradient -----------------------------------------------------------------------------------
     @torch.no_grad()
-    def backward(self, d_emb: torch.Tensor) -> torch.Tensor:
-        """d_emb: dL/d(embedding) * self.gscale, fp32 [N, out_dim]  ->  dL/d(images), fp32 NCHW."""
+    def backward(self, d_emb: torch.Tensor, record: Optional[dict] = None) -> torch.Tensor:
+        """d_emb: dL/d(embedding) * self.gscale, fp32 [N, out_dim]  ->  dL/d(images), fp32 NCHW.
+        record (tests): a dict that receives references to gradient tensors this pass makes anyway (all times gscale; no launch, no copy):
+        g32 = the fp32 gradient at every block boundary, the last block's output first; gm32 = the one between a block's two branches, last
+        block first; g0 = the 16-bit gradient at the patch embedding; dcol = the fp32 im2col gradient."""
         sv = self.saved
         if sv is None:
             raise RuntimeError("call forward(images, save=True) before backward()")
@@ -284,6 +287,8 @@ class VitEngine:
         g32 = torch.zeros((m, width), dtype=torch.float32, device=dev)
         g16 = torch.zeros((m, width), dtype=tdt, device=dev)
         self._ln_bwd(dy_post, dy_post.shape[1], sv["x_final"], self.ln_post, sv["mr_post"], None, n, width, row_stride=t, g32=g32, g16=g16)
+        if record is not None:
+            record.update(g32=[g32], gm32=[])
         for blk, L in zip(reversed(self.blocks), reversed(sv["layers"])):
             # ---- MLP branch
             if ops.fused_mlp_epilogues(blk["pr"].bwd, m):    # dh * act'(h_pre) in the GEMM epilogue
@@ -324,11 +329,16 @@ class VitEngine:
                           sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * w3, d), dt=dt, d_off=width)       # dK
             dln1 = ops.igemm(dqkv, blk["qkv"].bwd, out_f32=True, defer_reduce=fuse)
             g32, g16 = self._ln_bwd_any(dln1, L["x_in"], blk["ln1"], L["mr1"], gm32, m, width)
+            if record is not None:
+                record["gm32"].append(gm32)
+                record["g32"].append(g32)
         _, g0 = self._ln_bwd(g32, width, sv["x0"], self.ln_pre, sv["mr_pre"], None, m, width, want32=False)
         dcol = torch.empty((n * (t - 1), self.kp), dtype=torch.float32, device=dev)
         ops.bgemm(g0, self.conv1.bwd.w, dcol, M=t - 1, N=self.kp, K=width, lda=width, ldb=width, ldd=self.kp, batch=n, batch_inner=1,
                   sA=(t * width, 0), sB=(0, 0), sD=((t - 1) * self.kp, 0), dt=dt, a_off=width)
         dres = torch.empty((n, 3, res, res), dtype=torch.float32, device=dev)
         call("pmi_unpatchify", ptr(dcol), ptr(self.std), ptr(dres), n, res, patch, self.kp, 1.0 / self.gscale)
+        if record is not None:
+            record.update(g0=g0, dcol=dcol)
         self.saved = None
         return _resize_backward(dres, sv["in_hw"])
