@@ -473,6 +473,26 @@ int pmi_style_level(const void* fa, const void* fb, const float* Ga, const float
 int pmi_gram_bwd(const void* fa, const void* fb, const void* S, void* T, const void* g_in, void* dF, int N, int HW, int C, float c_feat,
                  float c_gram, float gscale, int dtype, pmi_stream_t s);
 
+/* ---- Real-ESRGAN RRDBNet dense-block convolution (csrc/rrdb.hip), 16-bit NHWC, dtype 0 / 1, fp32 accumulation, forward only.
+ * pmi_rdb_conv3x3: one 3x3 / pad 1 / stride 1 convolution over the channel prefix [0, Cin) of X (pixel pitch ldx elements) into the N-channel
+ *   slice D (pixel pitch ldd), with everything the networks of perceptor/models/super_resolution/custom_rrdbnet_arch.py put around it:
+ *     z = conv(X)[pix][n] + bias[n];  a = z >= 0 ? z : slope z;  D[pix][n] = beta (alpha a + R1[pix][n]) + R2[pix][n]
+ *   in fp32 with one rounding at the store.  It replaces ResidualDenseBlock.forward (:32-39: conv1-4 + LeakyReLU write the slices
+ *   [64 + 32 (k - 1), + 32) of the dense buffer their own prefix lives in -- no torch.cat; conv5 with alpha = 0.2, R1 = x), RRDB.forward
+ *   (:56-61: the last conv5 also gets beta = 0.2, R2 = the RRDB's input), and of CustomRRDBNet.forward (:105-127) conv_body + skip
+ *   (R1 = feat), F.interpolate(scale_factor=2, mode="nearest") + conv_up* + LeakyReLU (up = 1: X is the half-size grid, read at
+ *   (y >> 1, x >> 1); H and W even) and conv_hr + LeakyReLU.  slope = 1: no activation.  R1 / R2 NULL: absent.
+ *   Cin a multiple of 32 in 32 .. 192, N 32 or 64; images, H, W >= 1 (any size: tiles are masked); pitches multiples of 8 and pointers
+ *   16-byte aligned; one image of X at most 2^31 - 16 bytes.  Wp: 16-bit weights in fragment order
+ *   [Cin / 32][tap = 3 ky + kx][N / 16][lane = 16 q + r][8] = W[16 nb + r][32 chunk + 8 q + j][ky][kx]; bias fp32 [N].
+ *   D may be channels of the buffer X points into as long as they lie outside [0, Cin); R1 may be X.  Only D's slice is written.
+ * pmi_rdb_conv3x3_eligible: host only, 1 when pmi_rdb_conv3x3 takes the shape (ldr = 0: that residual absent), else 0; pmi_rdb_conv3x3 then
+ *   (and for a misaligned or NULL pointer, or a non-finite scalar) returns PMI_ERR_ARG without a launch. */
+int pmi_rdb_conv3x3_eligible(int Cin, int N, int ldx, int ldd, int ldr1, int ldr2, int up, int images, int H, int W, int dtype);
+int pmi_rdb_conv3x3(const void* X, int ldx, int Cin, const void* Wp, const float* bias, int N, void* D, int ldd, const void* R1, int ldr1,
+                    const void* R2, int ldr2, float alpha, float beta, float slope, int up, int images, int H, int W, int dtype,
+                    pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

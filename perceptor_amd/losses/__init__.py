@@ -6,3 +6,4 @@ from .pixel import Resize, Smoothness
 from .spherical_distance import SphericalDistance
 from .shared_tower import tower_loss_and_grad
 from .style_transfer import StyleTransfer
+from .super_resolution import SuperResolution

@@ -6,3 +6,4 @@ from .stable_diffusion import StableDiffusion
 from .transformers_openai_clip import TransformersOpenAICLIP
 from .simulacra_aesthetic import SimulacraAesthetic
 from .vgg import VGG19
+from .super_resolution import SuperResolution

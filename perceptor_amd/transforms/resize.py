@@ -82,6 +82,20 @@ def band_tables(in_sz: int, out_sz: int, method: str):
     return idx.contiguous(), w.contiguous(), idx_t.contiguous(), w_t.contiguous()
 
 
+@lru_cache(maxsize=64)
+def bilinear_tables(in_sz: int, out_sz: int):
+    """(idx [out,2] int32, w [out,2] f32) on CPU: F.interpolate(mode="bilinear", align_corners=False) along one axis as a 2-tap band
+    for pmi_resize_apply.  Source position (j + 0.5) in / out - 0.5 clamped at 0, taps floor and floor + 1 (clamped to the last row),
+    weights 1 - t and t: no antialiasing, edge rows repeated (ATen's area_pixel_compute_source_index and its index clamp)."""
+    src = ((torch.arange(out_sz, dtype=torch.float64) + 0.5) * (in_sz / out_sz) - 0.5).clamp(min=0.0)
+    i0 = src.floor().long().clamp(max=in_sz - 1)
+    i1 = (i0 + 1).clamp(max=in_sz - 1)
+    t = (src - i0).clamp(0.0, 1.0)
+    idx = torch.stack([i0, i1], 1).int()
+    w = torch.stack([1.0 - t, t], 1).float()
+    return idx.contiguous(), w.contiguous()
+
+
 _dev_cache = {}
 
 
@@ -105,19 +119,28 @@ def _apply(x: torch.Tensor, idx, w, axis: int, out_sz: int) -> torch.Tensor:
     return out
 
 
-def _plan(h: int, w: int, out_shape: Tuple[int, int]):
+_RESAMPLE = {"bicubic": "cubic", "cubic": "cubic", "lanczos3": "lanczos3"}
+
+
+def _plan(h: int, w: int, out_shape: Tuple[int, int], resample=None):
     oh, ow = out_shape
-    method = "lanczos3" if (h >= oh and w >= ow) else "cubic"
+    if resample is None:
+        method = "lanczos3" if (h >= oh and w >= ow) else "cubic"
+    elif resample in _RESAMPLE:
+        method = _RESAMPLE[resample]
+    else:
+        raise ValueError(f"resize: resample {resample!r} is not one of {sorted(_RESAMPLE)} or None")
     dims = sorted([(oh / h, 2, h, oh), (ow / w, 3, w, ow)], key=lambda z: z[0])
     return method, [d for d in dims if d[0] != 1.0]
 
 
-def resize(images: torch.Tensor, out_shape: Tuple[int, int]) -> torch.Tensor:
-    """Forward resize of NCHW fp32 images on the HIP device."""
+def resize(images: torch.Tensor, out_shape: Tuple[int, int], resample=None) -> torch.Tensor:
+    """Forward resize of NCHW fp32 images on the HIP device.  resample: None (the reference's default rule, module doc), "bicubic" or
+    "lanczos3" (the reference's ``resample=`` names, resize_right.py:102-110)."""
     if not images.is_cuda:
         raise RuntimeError("perceptor_amd.transforms.resize runs on a HIP device only (no CPU fallback)")
     x = images.float().contiguous()
-    method, dims = _plan(x.shape[2], x.shape[3], out_shape)
+    method, dims = _plan(x.shape[2], x.shape[3], out_shape, resample)
     for _, axis, i, o in dims:
         idx, w, _, _ = _tables_on(x.device, i, o, method)
         x = _apply(x, idx, w, axis, o)
