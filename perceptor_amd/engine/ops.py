@@ -892,12 +892,87 @@ def upsample_bilinear2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
     return _up2_bwd("pmi_upsample_bilinear2_bwd", "pmi_split_upsample_bilinear2_bwd", g, dt)
 
 
+def _transpose16(src: torch.Tensor, rows: int, cols: int, ld: int, s_o: int, s_i: int, inner: int, batch: int) -> torch.Tensor:
+    """[batch, cols, rows padded to 8] 16-bit: block z = (o, i) of src, [rows, cols] with row pitch ld at element o * s_o + i * s_i, transposed."""
+    rp = (rows + 7) // 8 * 8
+    out = _empty((batch, cols, rp), src.dtype, src.device)
+    call("pmi_transpose_16", ptr(src), ptr(out), rows, cols, ld, s_o, s_i, inner, batch)
+    return out
+
+
+def _heads_t(x: torch.Tensor, heads: int, d: int, hs: int) -> torch.Tensor:
+    """The heads of a token-major operand, each transposed: x [N, R, .] -> [N*heads, d, Rp]."""
+    n, r, ld = x.shape[0], x.shape[1], x.stride(1)
+    return _transpose16(x, r, d, ld, r * ld, hs, heads, n * heads)
+
+
+def _scores_t(s: torch.Tensor, cols: int, heads: int) -> torch.Tensor:
+    """A score-shaped matrix transposed per head: s [N*heads, R, >= cols] -> [N*heads, cols, Rp]."""
+    nh, r, ld = s.shape
+    return _transpose16(s, r, cols, ld, heads * r * ld, r * ld, heads, nh)
+
+
+def _heads_scores(a: torch.Tensor, b: torch.Tensor, heads: int, d: int, hs: int, dt: int) -> torch.Tensor:
+    """a_h b_h^T per (sample, head) of two token-major operands a [N, T, .] and b [N, Tk, .] -> fp32 [N*heads, T, Tkp]."""
+    n, t, tk = a.shape[0], a.shape[1], b.shape[1]
+    tkp = (tk + 7) // 8 * 8
+    s = _empty((n * heads, t, tkp), torch.float32, a.device)
+    return bgemm(a, b, s, M=t, N=tk, K=d, lda=a.stride(1), ldb=b.stride(1), ldd=tkp, batch=n * heads, batch_inner=heads,
+                 sA=(t * a.stride(1), hs), sB=(tk * b.stride(1), hs), sD=(heads * t * tkp, t * tkp), dt=dt)
+
+
+def _heads_product(a: torch.Tensor, bt: torch.Tensor, dst: torch.Tensor, heads: int, d: int, dt: int) -> None:
+    """Head h of the token-major dst [N, M, .] = a_z bt_z^T, z = (sample, head): a [N*heads, M, Kp] is a score-shaped matrix or its _scores_t,
+    bt [N*heads, d, Kp] a _heads_t; Kp is the inner length padded to 8."""
+    nh, m, kp = a.shape
+    ld = dst.stride(1)
+    bgemm(a, bt, dst, M=m, N=d, K=kp, lda=kp, ldb=kp, ldd=ld, batch=nh, batch_inner=heads,
+          sA=(heads * m * kp, m * kp), sB=(heads * d * kp, d * kp), sD=(m * ld, d), dt=dt)
+
+
+def _gemm_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, d: int, dt: int, hs: Optional[int] = None,
+                    causal: bool = False):
+    """softmax(q k^T d^-1/2) v as two batched MFMA GEMMs, an fp32 softmax and a transpose: the route of every head dim the flash kernels do
+    not take, and the one that keeps the softmax for _gemm_attention_backward.  q [N, T, .], k and v [N, Tk, .] are (views of) 16-bit tensors
+    as flash_attention takes them: stride(1) is the leading dimension, data_ptr() carries the channel offset and head h sits at channels
+    [h*hs, h*hs + d) of the view (hs = d by default; 3*d for channels ordered (head, {q,k,v}, d)).
+    -> (out [N, T, heads*d], P [N*heads, T, Tkp] 16-bit with zero pad columns, Tkp = Tk rounded up to 8)."""
+    hs = hs or d
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    n, t, tk = q.shape[0], q.shape[1], k.shape[1]
+    s = _heads_scores(q, k, heads, d, hs, dt)
+    p = _empty(tuple(s.shape), q.dtype, q.device)
+    call("pmi_softmax_causal_fwd" if causal else "pmi_softmax_fwd", ptr(s), ptr(p), n * heads * t, tk, s.shape[2], s.shape[2], float(d) ** -0.5, dt)
+    out = _empty((n, t, heads * d), q.dtype, q.device)
+    _heads_product(p, _heads_t(v, heads, d, hs), out, heads, d, dt)
+    return out, p
+
+
+def _gemm_attention_backward(q: Optional[torch.Tensor], k: torch.Tensor, v: torch.Tensor, p: torch.Tensor, d_out: torch.Tensor, heads: int,
+                             d: int, dt: int, dq: torch.Tensor, dk: Optional[torch.Tensor] = None, dv: Optional[torch.Tensor] = None) -> None:
+    """The gradient of _gemm_attention (hs = d) from d loss / d out [N, T, heads*d] and the kept softmax P, written into the token-major
+    destination views dq [N, T, .] and dk, dv [N, Tk, .] (16-bit or fp32; the three slices of one dqkv, or dq and the halves of an fp32 dkv).
+    The five products autograd forms: dP = dO V^T, dS = softmax'(P, dP) with the scale folded in, dV = P^T dO, dQ = dS K, dK = dS^T Q.
+    With dk and dv None dq alone is written and q may be None."""
+    assert (dk is None) == (dv is None) and (dk is None or q is not None), "dk and dv come as a pair, and need q"
+    assert all(x.stride(2) == 1 for x in (q, k, v, d_out, dq, dk, dv) if x is not None)
+    tk = k.shape[1]
+    dp = _heads_scores(d_out, v, heads, d, d, dt)
+    ds = _empty(tuple(dp.shape), d_out.dtype, d_out.device)
+    call("pmi_softmax_bwd", ptr(dp), ptr(p), ptr(ds), dp.shape[0] * dp.shape[1], tk, dp.shape[2], dp.shape[2], float(d) ** -0.5, dt)
+    if dv is not None:
+        _heads_product(_scores_t(p, tk, heads), _heads_t(d_out, heads, d, d), dv, heads, d, dt)
+    _heads_product(ds, _heads_t(k, heads, d, d), dq, heads, d, dt)
+    if dk is not None:
+        _heads_product(_scores_t(ds, tk, heads), _heads_t(q, heads, d, d), dk, heads, d, dt)
+
+
 def attention(qkv: torch.Tensor, heads: int, order: int, dt: int, causal: bool = False) -> torch.Tensor:
     """Self-attention over tokens.  qkv: [N, T, 3C] 16-bit -> [N, T, C].
     causal: query i sees keys 0..i (the CLIP text tower's mask, ruclip/model.py:181-185); runs the batched-GEMM path.
 
     order 0: channels = (head, {q,k,v}, d) (unet.py:332-348); order 1: ({q,k,v}, head, d).
-    Head dim 64 runs the fused flash kernel; other head dims use batched MFMA GEMMs + softmax.
+    Head dim 64 runs the fused flash kernel; other head dims flash_attention (order 1, up to d = 160) or _gemm_attention.
     """
     if dt == DT_F16X2:
         if causal:
@@ -907,67 +982,55 @@ def attention(qkv: torch.Tensor, heads: int, order: int, dt: int, causal: bool =
     c = c3 // 3
     d = c // heads
     dev = qkv.device
-    out = _empty((n, t, c), qkv.dtype, dev)
-    scale = float(d) ** -0.5
     if d == 64 and not causal:
         tp = (t + 31) // 32 * 32
         q = _empty((n * heads, tp, 64), qkv.dtype, dev)
         k = _empty((n * heads, tp, 64), qkv.dtype, dev)
         vt = _empty((n * heads, 64, tp), qkv.dtype, dev)
+        out = _empty((n, t, c), qkv.dtype, dev)
         call("pmi_qkv_split", ptr(qkv), ptr(q), ptr(k), ptr(vt), n, t, heads, order, dt)
-        call("pmi_attn_d64", ptr(q), ptr(k), ptr(vt), ptr(out), n, t, heads, scale, dt)
+        call("pmi_attn_d64", ptr(q), ptr(k), ptr(vt), ptr(out), n, t, heads, float(d) ** -0.5, dt)
         return out
     assert d % 8 == 0, "head dim must be a multiple of 8"
     if FLASH_ENABLED and order == 1 and not causal and d <= 160:
         return flash_attention(qkv, qkv[..., c:], qkv[..., 2 * c:], heads, d, dt)
-    tp = (t + 7) // 8 * 8
     if order == 0:
-        qo, ko, vo, hs = 0, d, 2 * d, 3 * d
+        return _gemm_attention(qkv, qkv[..., d:], qkv[..., 2 * d:], heads, d, dt, hs=3 * d, causal=causal)[0]
+    return _gemm_attention(qkv, qkv[..., c:], qkv[..., 2 * c:], heads, d, dt, causal=causal)[0]
+
+
+def _flash_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, d: int, dt: int, lse: Optional[torch.Tensor] = None):
+    """pmi_attn_flash, or with lse [N*heads, Tp32] fp32 pmi_attn_flash_train, which also leaves the log-sum-exp there: (out, the fragment
+    workspace).  The same kernels and output bits either way."""
+    n, t = q.shape[:2]
+    tk = k.shape[1]
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and k.stride(1) == v.stride(1)
+    assert q.stride(0) == t * q.stride(1) and k.stride(0) == tk * k.stride(1)
+    kib = _hip.lib().pmi_attn_flash_workspace(n, t, tk, heads, d)
+    if kib < 0:
+        raise ValueError(f"flash attention: unsupported head dim {d}")
+    ws = _empty((kib * 512,), q.dtype, q.device)
+    out = _empty((n, t, heads * d), q.dtype, q.device)
+    if lse is None:
+        call("pmi_attn_flash", ptr(q), q.stride(1), ptr(k), ptr(v), k.stride(1), ptr(out), ptr(ws), n, t, tk, heads, d, float(d) ** -0.5, dt)
     else:
-        qo, ko, vo, hs = 0, c, 2 * c, d
-    s = _empty((n * heads, t, tp), torch.float32, dev)
-    bgemm(qkv, qkv, s, M=t, N=t, K=d, lda=c3, ldb=c3, ldd=tp, batch=n * heads, batch_inner=heads,
-          sA=(t * c3, hs), sB=(t * c3, hs), sD=(heads * t * tp, t * tp), dt=dt, a_off=qo, b_off=ko)
-    p = _empty((n * heads, t, tp), qkv.dtype, dev)
-    call("pmi_softmax_causal_fwd" if causal else "pmi_softmax_fwd", ptr(s), ptr(p), n * heads * t, t, tp, tp, scale, dt)
-    vt = _empty((n * heads, d, tp), qkv.dtype, dev)
-    call("pmi_transpose_16", qkv.data_ptr() + vo * qkv.element_size(), ptr(vt), t, d, c3, t * c3, hs, heads, n * heads)
-    bgemm(p, vt, out, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=c, batch=n * heads, batch_inner=heads,
-          sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * c, d), dt=dt)
-    return out
+        call("pmi_attn_flash_train", ptr(q), q.stride(1), ptr(k), ptr(v), k.stride(1), ptr(out), ptr(ws), ptr(lse), n, t, tk, heads, d,
+             float(d) ** -0.5, dt)
+    return out, ws
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, d: int, dt: int) -> torch.Tensor:
     """softmax(q k^T d^-1/2) v through pmi_attn_flash.  q [N, T, >= heads*d] and k, v [N, Tk, >= heads*d] are (views of) 16-bit tensors
     whose last-dim stride is 1 and whose head h sits at channels [h*d, (h+1)*d) of the view; -> [N, T, heads*d]."""
-    n, t = q.shape[:2]
-    tk = k.shape[1]
-    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and k.stride(1) == v.stride(1)
-    assert q.stride(0) == t * q.stride(1) and k.stride(0) == tk * k.stride(1)
-    kib = _hip.lib().pmi_attn_flash_workspace(n, t, tk, heads, d)
-    if kib < 0:
-        raise ValueError(f"flash attention: unsupported head dim {d}")
-    ws = _empty((kib * 512,), q.dtype, q.device)
-    out = _empty((n, t, heads * d), q.dtype, q.device)
-    call("pmi_attn_flash", ptr(q), q.stride(1), ptr(k), ptr(v), k.stride(1), ptr(out), ptr(ws), n, t, tk, heads, d, float(d) ** -0.5, dt)
-    return out
+    return _flash_forward(q, k, v, heads, d, dt)[0]
 
 
 def flash_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, d: int, dt: int):
-    """flash_attention keeping what flash_attention_backward needs: (out, saved).  Same kernels and output bits as flash_attention; kept are
-    the operand views, the forward's fragment workspace, the output and lse [N*heads, Tp] fp32 (exp2 domain) -- no probabilities."""
-    n, t = q.shape[:2]
-    tk = k.shape[1]
-    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and k.stride(1) == v.stride(1)
-    assert q.stride(0) == t * q.stride(1) and k.stride(0) == tk * k.stride(1)
-    kib = _hip.lib().pmi_attn_flash_workspace(n, t, tk, heads, d)
-    if kib < 0:
-        raise ValueError(f"flash attention: unsupported head dim {d}")
-    ws = _empty((kib * 512,), q.dtype, q.device)
-    lse = _empty((n * heads, (t + 31) // 32 * 32), torch.float32, q.device)
-    out = _empty((n, t, heads * d), q.dtype, q.device)
-    call("pmi_attn_flash_train", ptr(q), q.stride(1), ptr(k), ptr(v), k.stride(1), ptr(out), ptr(ws), ptr(lse), n, t, tk, heads, d,
-         float(d) ** -0.5, dt)
+    """flash_attention keeping what flash_attention_backward needs: (out, saved).  Same kernels and output bits as flash_attention
+    (_flash_forward); kept are the operand views, the forward's fragment workspace, the output and lse [N*heads, Tp] fp32 (exp2 domain) --
+    no probabilities."""
+    lse = _empty((q.shape[0] * heads, (q.shape[1] + 31) // 32 * 32), torch.float32, q.device)
+    out, ws = _flash_forward(q, k, v, heads, d, dt, lse)
     return out, (q, k, v, ws, lse, out)
 
 
@@ -1009,54 +1072,21 @@ def flash_attention_backward(saved, d_out: torch.Tensor, heads: int, d: int, dt:
 
 
 def cross_attention_train(q: torch.Tensor, kv: torch.Tensor, heads: int, dt: int):
-    """cross_attention's batched-GEMM route keeping the softmax: (out [N, T, C], P [N*heads, T, Tcp] 16-bit)."""
-    n, t, c = q.shape
-    tc = kv.shape[1]
-    d = c // heads
-    tcp = (tc + 7) // 8 * 8
-    dev = q.device
-    s = _empty((n * heads, t, tcp), torch.float32, dev)
-    bgemm(q, kv, s, M=t, N=tc, K=d, lda=c, ldb=2 * c, ldd=tcp, batch=n * heads, batch_inner=heads,
-          sA=(t * c, d), sB=(tc * 2 * c, d), sD=(heads * t * tcp, t * tcp), dt=dt)
-    p = _empty((n * heads, t, tcp), q.dtype, dev)
-    call("pmi_softmax_fwd", ptr(s), ptr(p), n * heads * t, tc, tcp, tcp, float(d) ** -0.5, dt)
-    vt = _transpose16(kv, c, tc, d, 2 * c, tc * 2 * c, d, heads, n * heads)
-    out = _empty((n, t, c), q.dtype, dev)
-    bgemm(p, vt, out, M=t, N=d, K=tcp, lda=tcp, ldb=tcp, ldd=c, batch=n * heads, batch_inner=heads,
-          sA=(heads * t * tcp, t * tcp), sB=(heads * d * tcp, d * tcp), sD=(t * c, d), dt=dt)
-    return out, p
+    """cross_attention's batched-GEMM route keeping the softmax (_gemm_attention): (out [N, T, C], P [N*heads, T, Tcp] 16-bit)."""
+    c = q.shape[2]
+    return _gemm_attention(q, kv, kv[..., c:], heads, c // heads, dt)
 
 
 def cross_attention_backward(kv: torch.Tensor, p: torch.Tensor, d_out: torch.Tensor, heads: int, dt: int, q: Optional[torch.Tensor] = None):
-    """d loss / d q [N, T, C] of cross_attention_train from the kept softmax: dP = dO V^T, dS = softmax'(P, dP), dQ = dS K.  With q (the
-    forward's queries; a differentiable prompt) also d loss / d kv: (dq, dkv [N, Tc, 2C] fp32), dV = P^T dO and dK = dS^T Q through the same
-    batched GEMMs, fp32 out as flash_attention_backward's."""
+    """d loss / d q [N, T, C] of cross_attention_train from the kept softmax (_gemm_attention_backward).  With q (the forward's queries; a
+    differentiable prompt) also d loss / d kv: (dq, dkv [N, Tc, 2C] fp32 in the layout of kv), fp32 out as flash_attention_backward's."""
     n, t, c = d_out.shape
-    tc = kv.shape[1]
-    d = c // heads
-    tcp = (tc + 7) // 8 * 8
-    dev = d_out.device
-    dp = _empty((n * heads, t, tcp), torch.float32, dev)
-    bgemm(d_out, kv, dp, M=t, N=tc, K=d, lda=c, ldb=2 * c, ldd=tcp, batch=n * heads, batch_inner=heads,
-          sA=(t * c, d), sB=(tc * 2 * c, d), sD=(heads * t * tcp, t * tcp), dt=dt, b_off=c)
-    ds = _empty((n * heads, t, tcp), d_out.dtype, dev)
-    call("pmi_softmax_bwd", ptr(dp), ptr(p), ptr(ds), n * heads * t, tc, tcp, tcp, float(d) ** -0.5, dt)
-    kt = _transpose16(kv, 0, tc, d, 2 * c, tc * 2 * c, d, heads, n * heads)
-    dq = _empty((n, t, c), d_out.dtype, dev)
-    bgemm(ds, kt, dq, M=t, N=d, K=tcp, lda=tcp, ldb=tcp, ldd=c, batch=n * heads, batch_inner=heads,
-          sA=(heads * t * tcp, t * tcp), sB=(heads * d * tcp, d * tcp), sD=(t * c, d), dt=dt)
+    dq = _empty((n, t, c), d_out.dtype, d_out.device)
     if q is None:
+        _gemm_attention_backward(None, kv, kv[..., c:], p, d_out, heads, c // heads, dt, dq)
         return dq
-    tp = (t + 7) // 8 * 8
-    dkv = _empty((n, tc, 2 * c), torch.float32, dev)
-    pt = _transpose16(p, 0, t, tc, tcp, heads * t * tcp, t * tcp, heads, n * heads)             # [N*heads, Tc, Tp]
-    dot = _transpose16(d_out, 0, t, d, c, t * c, d, heads, n * heads)                             # [N*heads, d, Tp]
-    bgemm(pt, dot, dkv, M=tc, N=d, K=tp, lda=tp, ldb=tp, ldd=2 * c, batch=n * heads, batch_inner=heads,
-          sA=(heads * tc * tp, tc * tp), sB=(heads * d * tp, d * tp), sD=(tc * 2 * c, d), dt=dt, d_off=c)          # dV
-    dst = _transpose16(ds, 0, t, tc, tcp, heads * t * tcp, t * tcp, heads, n * heads)
-    qt = _transpose16(q, 0, t, d, c, t * c, d, heads, n * heads)
-    bgemm(dst, qt, dkv, M=tc, N=d, K=tp, lda=tp, ldb=tp, ldd=2 * c, batch=n * heads, batch_inner=heads,
-          sA=(heads * tc * tp, tc * tp), sB=(heads * d * tp, d * tp), sD=(tc * 2 * c, d), dt=dt)                   # dK
+    dkv = _empty((n, kv.shape[1], 2 * c), torch.float32, d_out.device)
+    _gemm_attention_backward(q, kv, kv[..., c:], p, d_out, heads, c // heads, dt, dq, dkv, dkv[..., c:])
     return dq, dkv
 
 
@@ -1069,81 +1099,30 @@ def geglu_backward(h: torch.Tensor, dg: torch.Tensor, dt: int) -> torch.Tensor:
 
 def cross_attention(q: torch.Tensor, kv: torch.Tensor, heads: int, dt: int) -> torch.Tensor:
     """softmax(q k^T d^-1/2) v with keys / values from another sequence (stable_diffusion/attention.py:268-298, the fused call at :285).
-    q [N, T, C], kv [N, Tc, 2C] = (k | v) x (head, d), 16-bit -> [N, T, C].  Batched MFMA GEMMs + fp32 softmax (Tc = 77 prompt tokens)."""
+    q [N, T, C], kv [N, Tc, 2C] = (k | v) x (head, d), 16-bit -> [N, T, C].  flash_attention up to d = 160, else _gemm_attention."""
     n, t, c = q.shape
-    tc = kv.shape[1]
     assert kv.shape[0] == n and kv.shape[2] == 2 * c
     d = c // heads
     assert d % 8 == 0, "head dim must be a multiple of 8"
     if FLASH_ENABLED and d <= 160:
         return flash_attention(q, kv, kv[..., c:], heads, d, dt)
-    tcp = (tc + 7) // 8 * 8
-    dev = q.device
-    s = _empty((n * heads, t, tcp), torch.float32, dev)
-    bgemm(q, kv, s, M=t, N=tc, K=d, lda=c, ldb=2 * c, ldd=tcp, batch=n * heads, batch_inner=heads,
-          sA=(t * c, d), sB=(tc * 2 * c, d), sD=(heads * t * tcp, t * tcp), dt=dt)
-    p = _empty((n * heads, t, tcp), q.dtype, dev)
-    call("pmi_softmax_fwd", ptr(s), ptr(p), n * heads * t, tc, tcp, tcp, float(d) ** -0.5, dt)
-    vt = _transpose16(kv, c, tc, d, 2 * c, tc * 2 * c, d, heads, n * heads)
-    out = _empty((n, t, c), q.dtype, dev)
-    bgemm(p, vt, out, M=t, N=d, K=tcp, lda=tcp, ldb=tcp, ldd=c, batch=n * heads, batch_inner=heads,
-          sA=(heads * t * tcp, t * tcp), sB=(heads * d * tcp, d * tcp), sD=(t * c, d), dt=dt)
-    return out
-
-
-def _transpose16(src: torch.Tensor, off: int, rows: int, cols: int, ld: int, s_o: int, s_i: int, inner: int, batch: int) -> torch.Tensor:
-    rp = (rows + 7) // 8 * 8
-    out = _empty((batch, cols, rp), src.dtype, src.device)
-    call("pmi_transpose_16", src.data_ptr() + off * src.element_size(), ptr(out), rows, cols, ld, s_o, s_i, inner, batch)
-    return out
+    return _gemm_attention(q, kv, kv[..., c:], heads, d, dt)[0]
 
 
 def attention_train(qkv: torch.Tensor, heads: int, dt: int):
     """Self-attention for any head dim, channels (q|k|v, head, d), keeping the softmax for attention_backward:
-    qkv [N, T, 3C] 16-bit -> (out [N, T, C], P [N*heads, T, Tp] 16-bit).  Batched MFMA GEMMs + softmax (as `attention`, order 1)."""
-    n, t, c3 = qkv.shape
-    c = c3 // 3
-    d = c // heads
-    tp = (t + 7) // 8 * 8
-    dev = qkv.device
-    sc = _empty((n * heads, t, tp), torch.float32, dev)
-    bgemm(qkv, qkv, sc, M=t, N=t, K=d, lda=c3, ldb=c3, ldd=tp, batch=n * heads, batch_inner=heads,
-          sA=(t * c3, d), sB=(t * c3, d), sD=(heads * t * tp, t * tp), dt=dt, b_off=c)
-    p = _empty((n * heads, t, tp), qkv.dtype, dev)
-    call("pmi_softmax_fwd", ptr(sc), ptr(p), n * heads * t, t, tp, tp, float(d) ** -0.5, dt)
-    vt = _transpose16(qkv, 2 * c, t, d, c3, t * c3, d, heads, n * heads)
-    out = _empty((n, t, c), qkv.dtype, dev)
-    bgemm(p, vt, out, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=c, batch=n * heads, batch_inner=heads,
-          sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * c, d), dt=dt)
-    return out, p
+    qkv [N, T, 3C] 16-bit -> (out [N, T, C], P [N*heads, T, Tp] 16-bit) by _gemm_attention."""
+    c = qkv.shape[2] // 3
+    return _gemm_attention(qkv, qkv[..., c:], qkv[..., 2 * c:], heads, c // heads, dt)
 
 
 def attention_backward(qkv: torch.Tensor, p: torch.Tensor, d_out: torch.Tensor, heads: int, dt: int) -> torch.Tensor:
-    """d loss / d qkv [N, T, 3C] from d loss / d out [N, T, C] and the saved softmax P (the same five products autograd forms:
-    dP = dO V^T, dS = softmax'(P, dP), dV = P^T dO, dQ = dS K, dK = dS^T Q, scale folded into softmax_bwd)."""
+    """d loss / d qkv [N, T, 3C] from d loss / d out [N, T, C] and attention_train's softmax P (_gemm_attention_backward)."""
     n, t, c3 = qkv.shape
     c = c3 // 3
-    d = c // heads
-    tp = (t + 7) // 8 * 8
-    dev = qkv.device
-    da = d_out.reshape(n * t, c)
-    dqkv = _empty((n, t, c3), qkv.dtype, dev)
-    dp = _empty((n * heads, t, tp), torch.float32, dev)
-    bgemm(da, qkv, dp, M=t, N=t, K=d, lda=c, ldb=c3, ldd=tp, batch=n * heads, batch_inner=heads,
-          sA=(t * c, d), sB=(t * c3, d), sD=(heads * t * tp, t * tp), dt=dt, b_off=2 * c)
-    ds = _empty((n * heads, t, tp), qkv.dtype, dev)
-    call("pmi_softmax_bwd", ptr(dp), ptr(p), ptr(ds), n * heads * t, t, tp, tp, float(d) ** -0.5, dt)
-    pt = _transpose16(p, 0, t, t, tp, heads * t * tp, t * tp, heads, n * heads)
-    dot = _transpose16(da, 0, t, d, c, t * c, d, heads, n * heads)
-    bgemm(pt, dot, dqkv, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=c3, batch=n * heads, batch_inner=heads,
-          sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * c3, d), dt=dt, d_off=2 * c)        # dV
-    kt = _transpose16(qkv, c, t, d, c3, t * c3, d, heads, n * heads)
-    bgemm(ds, kt, dqkv, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=c3, batch=n * heads, batch_inner=heads,
-          sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * c3, d), dt=dt)                     # dQ
-    dst = _transpose16(ds, 0, t, t, tp, heads * t * tp, t * tp, heads, n * heads)
-    qt = _transpose16(qkv, 0, t, d, c3, t * c3, d, heads, n * heads)
-    bgemm(dst, qt, dqkv, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=c3, batch=n * heads, batch_inner=heads,
-          sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * c3, d), dt=dt, d_off=c)            # dK
+    dqkv = _empty((n, t, c3), qkv.dtype, qkv.device)
+    _gemm_attention_backward(qkv, qkv[..., c:], qkv[..., 2 * c:], p, d_out.reshape(n, t, c), heads, c // heads, dt,
+                             dqkv, dqkv[..., c:], dqkv[..., 2 * c:])
     return dqkv
 
 
@@ -1209,56 +1188,43 @@ def linear_f32(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     return gemm_f32(x, weight, out, M=m, N=n, K=k, lda=x.stride(0), ldb=weight.stride(0), ldd=n, bias=bias, act=act, residual=residual)
 
 
-def attention_precise(qkv: torch.Tensor, heads: int, order: int) -> torch.Tensor:
-    """Self-attention in precise mode: qkv is a precise tensor [N, T, 2*3C]; scores, softmax and values in exact fp32
-    (both operands of these products are activations, so the hi + lo weight trick does not apply); returns a precise [N, T, 2C]."""
-    n, t, c6 = qkv.shape
-    c3 = c6 // 2
-    c = c3 // 3
-    d = c // heads
-    dev = qkv.device
-    q32 = _empty((n, t, c3), torch.float32, dev)
-    call("pmi_split_to_f32", ptr(qkv), ptr(q32), n * t, c3)
-    if order == 0:
-        qo, ko, vo, hs = 0, d, 2 * d, 3 * d
-    else:
-        qo, ko, vo, hs = 0, c, 2 * c, d
-    s = _empty((n * heads, t, t), torch.float32, dev)
-    gemm_f32(q32, q32, s, M=t, N=t, K=d, lda=c3, ldb=c3, ldd=t, batch=n * heads, batch_inner=heads,
-             sA=(t * c3, hs), sB=(t * c3, hs), sD=(heads * t * t, t * t), a_off=qo, b_off=ko)
-    call("pmi_softmax_f32", ptr(s), n * heads * t, t, t, float(d) ** -0.5)
-    o32 = _empty((n, t, c), torch.float32, dev)
-    gemm_f32(s, q32, o32, M=t, N=d, K=t, lda=t, ldb=c3, ldd=c, trans_b=True, batch=n * heads, batch_inner=heads,
-             sA=(heads * t * t, t * t), sB=(t * c3, hs), sD=(t * c, d), b_off=vo)
-    out = _empty((n, t, 2 * c), torch.float16, dev)
-    call("pmi_split_from_f32", ptr(o32), c, ptr(out), n * t, c)
-    return out
-
-
-def attention_precise_train(qkv: torch.Tensor, n: int, t: int, heads: int):
-    """self_attention_train in precise mode: qkv is a precise [N*T, 2*3C] tensor, channels (q|k|v, head, d) -> (precise out [N*T, 2C], saved).
-    The same three launches as attention_precise (order 1); the fp32 copy of q, k, v and the fp32 softmax P stay on the tape."""
+def _attention_precise(qkv: torch.Tensor, n: int, t: int, heads: int, order: int):
+    """Self-attention in precise mode: qkv is a precise tensor [N, T, 2*3C] or [N*T, 2*3C], channel order as `attention`; scores, softmax
+    and values in exact fp32 (both operands of these products are activations, so the hi + lo weight trick does not apply).
+    -> (precise out [.., 2C] with qkv's leading dims, (the fp32 copy of q, k, v [N, T, 3C], the fp32 softmax P [N*heads, T, T]))."""
     c3 = qkv.shape[-1] // 2
     c = c3 // 3
     d = c // heads
     dev = qkv.device
     q32 = _empty((n, t, c3), torch.float32, dev)
     call("pmi_split_to_f32", ptr(qkv), ptr(q32), n * t, c3)
+    ko, vo, hs = (d, 2 * d, 3 * d) if order == 0 else (c, 2 * c, d)
     p = _empty((n * heads, t, t), torch.float32, dev)
     gemm_f32(q32, q32, p, M=t, N=t, K=d, lda=c3, ldb=c3, ldd=t, batch=n * heads, batch_inner=heads,
-             sA=(t * c3, d), sB=(t * c3, d), sD=(heads * t * t, t * t), b_off=c)
+             sA=(t * c3, hs), sB=(t * c3, hs), sD=(heads * t * t, t * t), b_off=ko)
     call("pmi_softmax_f32", ptr(p), n * heads * t, t, t, float(d) ** -0.5)
     o32 = _empty((n, t, c), torch.float32, dev)
     gemm_f32(p, q32, o32, M=t, N=d, K=t, lda=t, ldb=c3, ldd=c, trans_b=True, batch=n * heads, batch_inner=heads,
-             sA=(heads * t * t, t * t), sB=(t * c3, d), sD=(t * c, d), b_off=2 * c)
-    out = _empty((n * t, 2 * c), torch.float16, dev)
+             sA=(heads * t * t, t * t), sB=(t * c3, hs), sD=(t * c, d), b_off=vo)
+    out = _empty(tuple(qkv.shape[:-1]) + (2 * c,), torch.float16, dev)
     call("pmi_split_from_f32", ptr(o32), c, ptr(out), n * t, c)
     return out, (q32, p)
 
 
+def attention_precise(qkv: torch.Tensor, heads: int, order: int) -> torch.Tensor:
+    """`attention` in precise mode (_attention_precise): qkv is a precise tensor [N, T, 2*3C]; returns a precise [N, T, 2C]."""
+    return _attention_precise(qkv, qkv.shape[0], qkv.shape[1], heads, order)[0]
+
+
+def attention_precise_train(qkv: torch.Tensor, n: int, t: int, heads: int):
+    """self_attention_train in precise mode (_attention_precise, order 1): qkv is a precise [N*T, 2*3C] tensor, channels (q|k|v, head, d) ->
+    (precise out [N*T, 2C], saved); the fp32 copy of q, k, v and the fp32 softmax P stay on the tape."""
+    return _attention_precise(qkv, n, t, heads, 1)
+
+
 def attention_precise_backward(saved, da: torch.Tensor, n: int, t: int, heads: int) -> torch.Tensor:
     """Precise d loss / d qkv [N*T, 2*3C], channels (q|k|v, head, d), from the precise d loss / d out [N*T, 2C]: the five products of
-    attention_backward in exact fp32 (pmi_gemm_f32), dS = scale P o (dP - rowsum(dP o P)) in place over dP (pmi_softmax_bwd_f32)."""
+    _gemm_attention_backward in exact fp32 (pmi_gemm_f32), dS = scale P o (dP - rowsum(dP o P)) in place over dP (pmi_softmax_bwd_f32)."""
     q32, p = saved
     c3 = q32.shape[-1]
     c = c3 // 3

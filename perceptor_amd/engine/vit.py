@@ -176,12 +176,6 @@ class VitEngine:
             return g32, g16
         return self._ln_bwd(dy, d, x, gb, mr, gres, m, d)
 
-    def _transpose(self, src: torch.Tensor, off: int, rows: int, cols: int, ld: int, s_o: int, s_i: int, inner: int, batch: int):
-        rp = (rows + 7) // 8 * 8
-        out = torch.empty((batch, cols, rp), dtype=src.dtype, device=src.device)
-        call("pmi_transpose_16", src.data_ptr() + off * src.element_size(), ptr(out), rows, cols, ld, s_o, s_i, inner, batch)
-        return out
-
     # ---- forward --------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, images: torch.Tensor, save: bool = False, features: bool = False):
@@ -196,7 +190,6 @@ class VitEngine:
         g = res // patch
         t = g * g + 1
         m = n * t
-        tp = (t + 7) // 8 * 8
         d = width // heads
         resized = _resize(images, (res, res))
         col = torch.empty((n * g * g, self.kp), dtype=tdt, device=dev)
@@ -206,7 +199,6 @@ class VitEngine:
         call("pmi_vit_assemble", ptr(pe), ptr(self.cls), ptr(self.pos), ptr(x0), n, t, width, 0)
         _, x, mr_pre = self._ln(x0, width, self.ln_pre, m, width, want16=False, want32=True)
         sv = dict(in_hw=tuple(images.shape[2:]), n=n, x0=x0, mr_pre=mr_pre, layers=[]) if save else None
-        scale = float(d) ** -0.5
         fuse = width % 256 == 0 and width <= 2048            # split-K reduce of the MLP's last GEMM + the next block's LayerNorm in one pass
         nxt = None                                           # (h, mr1) of this block when the previous block's tail already produced them
         for bi, blk in enumerate(self.blocks):
@@ -216,24 +208,8 @@ class VitEngine:
                 h, mr1 = nxt
                 nxt = None
             qkv = ops.igemm(h, blk["qkv"].fwd)                                    # [m, 3*width], (q|k|v) x (head, d)
-            a = torch.empty((m, width), dtype=tdt, device=dev)
-            fused = d == 64
-            if fused:   # flash-style kernels: no T x T matrix, no transposes (csrc/attn.hip)
-                tp32 = (t + 31) // 32 * 32
-                aws = torch.empty((6, n * heads, tp32, 64), dtype=tdt, device=dev)
-                lse = torch.empty((n * heads, tp32), dtype=torch.float32, device=dev)
-                call("pmi_vit_attn_fwd", ptr(qkv), ptr(aws), ptr(lse), ptr(a), n, t, heads, scale, dt)
-                p = None
-            else:
-                s = torch.empty((n * heads, t, tp), dtype=torch.float32, device=dev)
-                ops.bgemm(qkv, qkv, s, M=t, N=t, K=d, lda=3 * width, ldb=3 * width, ldd=tp, batch=n * heads, batch_inner=heads,
-                          sA=(t * 3 * width, d), sB=(t * 3 * width, d), sD=(heads * t * tp, t * tp), dt=dt, b_off=width)
-                p = torch.empty((n * heads, t, tp), dtype=tdt, device=dev)
-                call("pmi_softmax_fwd", ptr(s), ptr(p), n * heads * t, t, tp, tp, scale, dt)
-                vt = self._transpose(qkv, 2 * width, t, d, 3 * width, t * 3 * width, d, heads, n * heads)
-                ops.bgemm(p, vt, a, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=width, batch=n * heads, batch_inner=heads,
-                          sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * width, d), dt=dt)
-                aws = lse = None
+            # head dim 64: flash-style kernels, no T x T matrix, no transposes (csrc/attn.hip); else batched GEMMs that keep the softmax
+            a, kept = ops.self_attention_train(qkv, n, t, heads, dt)
             x_mid = ops.igemm(a, blk["out"].fwd, residual=x, out_f32=True)
             h2, _, mr2 = self._ln(x_mid, width, blk["ln2"], m, width)
             if ops.fused_mlp_epilogues(blk["fc"].fwd, m):    # activation in the GEMM epilogue; the pre-activation value is kept only for a backward pass
@@ -249,8 +225,13 @@ class VitEngine:
                 x_out, hn, mrn = self._ln_slabs(x_out, blk["pr"].fwd.b, x_mid, self.blocks[bi + 1]["ln1"], m, width)
                 nxt = (hn, mrn)
             if save:
-                sv["layers"].append(dict(x_in=x, mr1=mr1, qkv=qkv if not fused else None, p=p, aws=aws, lse=lse, a=a if fused else None,
-                                         x_mid=x_mid, mr2=mr2, hpre=hpre))
+                # attn goes back to ops.self_attention_backward as it came; its parts by name are what tests read (the other route's stay None)
+                L = dict(x_in=x, mr1=mr1, attn=kept, qkv=None, p=None, aws=None, lse=None, a=None, x_mid=x_mid, mr2=mr2, hpre=hpre)
+                if d == 64:
+                    L["aws"], L["lse"], L["a"] = kept
+                else:
+                    L["qkv"], L["p"] = kept
+                sv["layers"].append(L)
             x = x_out
         y16, y32, mr_post = self._ln(x, t * width, self.ln_post, n, width, want32=features)         # cls token rows only
         emb = ops.igemm(y16, self.proj.fwd, out_f32=True)
@@ -277,9 +258,6 @@ class VitEngine:
         g = res // patch
         t = g * g + 1
         m = n * t
-        tp = (t + 7) // 8 * 8
-        d = width // heads
-        scale = float(d) ** -0.5
         d16 = torch.empty((n, out), dtype=tdt, device=dev)
         d_emb = d_emb.contiguous()          # named: a temporary would be released before the launch is queued
         call("pmi_cast_f32_to_16", ptr(d_emb), ptr(d16), n * out, ACT_NONE, dt)
@@ -301,32 +279,7 @@ class VitEngine:
             gm32, gm16 = self._ln_bwd_any(dln2, L["x_mid"], blk["ln2"], L["mr2"], g32, m, width)
             # ---- attention branch
             da = ops.igemm(gm16, blk["out"].bwd)                                    # dO, [m, w] (head, d)
-            w3 = 3 * width
-            dqkv = torch.empty((m, w3), dtype=tdt, device=dev)
-            if L["aws"] is not None:
-                tp32 = (t + 31) // 32 * 32
-                bws = torch.empty((2, n * heads, tp32, 64), dtype=tdt, device=dev)
-                delta = torch.empty((n * heads, tp32), dtype=torch.float32, device=dev)
-                call("pmi_vit_attn_bwd", ptr(L["aws"]), ptr(L["lse"]), ptr(L["a"]), ptr(da), ptr(bws), ptr(delta), ptr(dqkv),
-                     n, t, heads, scale, dt)
-            else:
-                qkv, p = L["qkv"], L["p"]
-                dp = torch.empty((n * heads, t, tp), dtype=torch.float32, device=dev)
-                ops.bgemm(da, qkv, dp, M=t, N=t, K=d, lda=width, ldb=w3, ldd=tp, batch=n * heads, batch_inner=heads,
-                          sA=(t * width, d), sB=(t * w3, d), sD=(heads * t * tp, t * tp), dt=dt, b_off=2 * width)
-                ds = torch.empty((n * heads, t, tp), dtype=tdt, device=dev)
-                call("pmi_softmax_bwd", ptr(dp), ptr(p), ptr(ds), n * heads * t, t, tp, tp, scale, dt)
-                pt = self._transpose(p, 0, t, t, tp, heads * t * tp, t * tp, heads, n * heads)          # [nh, t(s), tp(t)]
-                dot = self._transpose(da, 0, t, d, width, t * width, d, heads, n * heads)               # [nh, d, tp]
-                ops.bgemm(pt, dot, dqkv, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=w3, batch=n * heads, batch_inner=heads,
-                          sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * w3, d), dt=dt, d_off=2 * width)   # dV
-                kt = self._transpose(qkv, width, t, d, w3, t * w3, d, heads, n * heads)
-                ops.bgemm(ds, kt, dqkv, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=w3, batch=n * heads, batch_inner=heads,
-                          sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * w3, d), dt=dt)                    # dQ
-                dst = self._transpose(ds, 0, t, t, tp, heads * t * tp, t * tp, heads, n * heads)
-                qt = self._transpose(qkv, 0, t, d, w3, t * w3, d, heads, n * heads)
-                ops.bgemm(dst, qt, dqkv, M=t, N=d, K=tp, lda=tp, ldb=tp, ldd=w3, batch=n * heads, batch_inner=heads,
-                          sA=(heads * t * tp, t * tp), sB=(heads * d * tp, d * tp), sD=(t * w3, d), dt=dt, d_off=width)       # dK
+            dqkv = ops.self_attention_backward(L["attn"], da, n, t, heads, dt)       # [m, 3w]
             dln1 = ops.igemm(dqkv, blk["qkv"].bwd, out_f32=True, defer_reduce=fuse)
             g32, g16 = self._ln_bwd_any(dln1, L["x_in"], blk["ln1"], L["mr1"], gm32, m, width)
             if record is not None:

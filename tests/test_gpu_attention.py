@@ -2,7 +2,8 @@
 
 A. pmi_vit_attn_fwd / pmi_vit_attn_bwd (flash, head dim 64, with the input gradient: ViT, ADM and v-diffusion guidance gradients).
 B. pmi_attn_flash (head dims 8..160, Tk != T, one-wave and LDS kernels: StableDiffusion self- and cross-attention).
-C. the batched-GEMM path for head dims != 64 (attention_train / attention_backward, causal attention), the softmax kernels,
+C. the batched-GEMM path for head dims != 64 (attention_train / attention_backward, cross_attention_train / cross_attention_backward,
+   causal attention), the softmax kernels,
    the precise-mode softmax and pmi_transpose_16.
 
 Bounds (tests/_ref64.py): max|got - ref| <= 1.5 u S per output, u the unit roundoff of the 16-bit type and S the elementwise worst-case
@@ -10,6 +11,8 @@ sum of the roundings the kernel performs -- P rounded to 16 bit before P.V and P
 taken from the 16-bit O -- evaluated in float64.  test_*_bounds_reject_defects checks, on the CPU, that the listed plausible defects
 exceed these bounds by at least 2x at the tested shapes.  Every output and caller-owned scratch buffer is filled with NaN before a call.
 """
+import contextlib
+
 import pytest
 import torch
 
@@ -278,6 +281,72 @@ def test_attention_train_backward(d, T, N, H, dtype):
     R.check(f"{tag} dQ", dq, r["dQ"], R.attn_tol(r, "dQ", dtype))
     R.check(f"{tag} dK", dk, r["dK"], R.attn_tol(r, "dK", dtype))
     R.check(f"{tag} dV", dv, r["dV"], R.attn_tol(r, "dV", dtype))
+
+
+@contextlib.contextmanager
+def _flash_off():
+    from perceptor_amd.engine import ops
+    old, ops.FLASH_ENABLED = ops.FLASH_ENABLED, False
+    try:
+        yield
+    finally:
+        ops.FLASH_ENABLED = old
+
+
+# T and Tk each below one pad unit of 8; the prompt length (Tk = 77 -> 80); the head dim at which the engines take this route (> 160)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("d,T,Tk,N,H", [(16, 5, 7, 2, 3), (40, 33, 77, 2, 3), (168, 50, 77, 1, 2)])
+def test_cross_attention_train_backward(d, T, Tk, N, H, dtype):
+    """ops.cross_attention_train + ops.cross_attention_backward (the batched-GEMM cross route: keys / values of another length, kv = (k | v))
+    against float64 autograd, without q (dQ alone) and with it (dQ, fp32 dK | dV); the saved P is the float64 softmax rounded once (test_attention_train_backward's bound) with zero pad columns; ops.cross_attention
+    with flash switched off is the same launches.  attn_tol is derived for 16-bit outputs, so it also bounds the fp32 dkv."""
+    from perceptor_amd.engine import ops
+    from perceptor_amd._hip import dtype_code
+    dev = _dev()
+    td, dt = R.TD[dtype], dtype_code(dtype)
+    q, k, v = R.attn_inputs(N * H, T, d, "peaked" if T == 33 else "last", dtype, seed=T + d, Tk=Tk)
+    g = torch.Generator().manual_seed(d)
+    dO = R.rnd(torch.randn(N * H, T, d, generator=g, dtype=torch.float64), dtype)
+    qd = _heads_to_tokens(q, N, H).to(td).to(dev)
+    kv = torch.cat([_heads_to_tokens(z, N, H) for z in (k, v)], -1).to(td).to(dev)
+    dOd = _heads_to_tokens(dO, N, H).to(td).to(dev)
+    out, p = ops.cross_attention_train(qd, kv, H, dt)
+    dq_only = ops.cross_attention_backward(kv, p, dOd, H, dt)
+    dq, dkv = ops.cross_attention_backward(kv, p, dOd, H, dt, q=qd)
+    with _flash_off():
+        plain = ops.cross_attention(qd, kv, H, dt)
+    torch.cuda.synchronize()
+    assert tuple(p.shape) == (N * H, T, (Tk + 7) // 8 * 8) and (p[..., Tk:] == 0).all(), "P pad columns must be zero"
+    assert torch.isfinite(out).all() and torch.isfinite(dq_only).all() and torch.isfinite(dkv).all()
+    assert dkv.dtype == torch.float32 and tuple(dkv.shape) == (N, Tk, 2 * H * d)
+    r = R.attn_ref(q, k, v, dO, d ** -0.5)
+    tag = f"cross_attention_train d={d} T={T} Tk={Tk} {N}x{H} {dtype}"
+    R.check(f"{tag} out", _tokens_to_heads(out.cpu(), N, H), r["O"], R.attn_tol(r, "O", dtype))
+    R.check(f"{tag} P", p[..., :Tk].cpu(), r["P"], R.U[dtype] * float(r["P"].max()) * 1.01)
+    R.check(f"{tag} dQ", _tokens_to_heads(dq_only.cpu(), N, H), r["dQ"], R.attn_tol(r, "dQ", dtype))
+    assert torch.equal(dq, dq_only), "dq with q given differs from the dq-only call"
+    dk, dv = (_tokens_to_heads(z, N, H) for z in dkv.cpu().split(H * d, -1))
+    R.check(f"{tag} dK", dk, r["dK"], R.attn_tol(r, "dK", dtype))
+    R.check(f"{tag} dV", dv, r["dV"], R.attn_tol(r, "dV", dtype))
+    assert torch.equal(plain, out), "cross_attention (flash off) and cross_attention_train differ"
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("T", [5, 50])
+def test_attention_gemm_route_is_attention_train(T, dtype):
+    """ops.attention(order=1) at d = 32 with flash switched off is attention_train's launches: the same bits."""
+    from perceptor_amd.engine import ops
+    from perceptor_amd._hip import dtype_code
+    dev = _dev()
+    N, H, d = 2, 3, 32
+    q, k, v = R.attn_inputs(N * H, T, d, "peaked", dtype, seed=T + d)
+    qkv = torch.cat([_heads_to_tokens(z, N, H) for z in (q, k, v)], -1).to(R.TD[dtype]).to(dev)
+    out, _ = ops.attention_train(qkv, H, dtype_code(dtype))
+    with _flash_off():
+        plain = ops.attention(qkv, H, 1, dtype_code(dtype))
+    torch.cuda.synchronize()
+    assert torch.isfinite(out).all()
+    assert torch.equal(plain, out)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
