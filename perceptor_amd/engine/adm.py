@@ -231,31 +231,36 @@ class AdmEngine:
             raise NotImplementedError("identity skip over a concatenated input does not occur in the shipped configs")
         return ops.igemm(h, w[l.p + ".conv2"], residual=x, res_up=l.up, prologue=prologue, want_stats=True)
 
-    def _res(self, l: _Res, x, x1, emb):
+    def _res(self, l: _Res, x, x1, emb, tape=None):
+        """ResBlock (unet.py:232-252).  Inference and training mode issue the same launches: with a tape, the block's record for _res_back
+        (its inputs, both norms' coefficients and partials, conv1's output) is appended to it."""
         cfg, dt, w = self.cfg, self.dt, self.w
         g1, b1 = w[l.p + ".gn1"]
         ecols = 2 * l.cout if cfg.use_scale_shift_norm else l.cout
         e = emb[:, l.emb_off:l.emb_off + ecols]
+        film = e if cfg.use_scale_shift_norm else None
         nb = None if cfg.use_scale_shift_norm else e
         skip, skip1 = x, x1
         if l.down:
             # SiLU(GN(x)) must be pooled AFTER the activation: streaming apply+pool kernel, then the conv
             if x1 is None:      # both pooled tensors from one pass over x
-                h, skip = ops.group_norm_pool_skip(x, g1, b1, 32, dt, act=ACT_SILU)
+                h, skip, gn1 = ops.group_norm_pool_skip_train(x, g1, b1, 32, dt, act=ACT_SILU)
+            elif tape is not None:
+                raise NotImplementedError("down-sampling ResBlock over a concatenated input does not occur in the shipped configs: it has no backward")
             else:
                 h = ops.group_norm(x, g1, b1, 32, dt, x1=x1, act=ACT_SILU, pool=True)
                 skip = ops.avgpool2(x, dt)
             h = ops.igemm(h, w[l.p + ".conv1"], nbias=nb, want_stats=True)
         else:
             # GroupNorm-apply + SiLU fused into the conv's patch staging (no activated copy in HBM)
-            ca, cb = ops.group_norm_coeffs(x, g1, b1, 32, dt, x1=x1)
-            h = ops.igemm(x, w[l.p + ".conv1"], a1=x1, up=l.up, nbias=nb, prologue=(ca, cb, ACT_SILU), want_stats=True)
+            gn1 = ops.group_norm_coeffs_train(x, g1, b1, 32, dt, x1=x1)
+            h = ops.igemm(x, w[l.p + ".conv1"], a1=x1, up=l.up, nbias=nb, prologue=(gn1[0], gn1[1], ACT_SILU), want_stats=True)
         g2, b2 = w[l.p + ".gn2"]
-        if cfg.use_scale_shift_norm:
-            ca, cb = ops.group_norm_coeffs(h, g2, b2, 32, dt, film=e, film_ld=emb.stride(0))
-        else:
-            ca, cb = ops.group_norm_coeffs(h, g2, b2, 32, dt)
-        return self._conv2(l, h, skip, skip1, (ca, cb, ACT_SILU))
+        gn2 = ops.group_norm_coeffs_train(h, g2, b2, 32, dt, film=film, film_ld=emb.stride(0) if film is not None else 0)
+        out = self._conv2(l, h, skip, skip1, (gn2[0], gn2[1], ACT_SILU))
+        if tape is not None:
+            tape.append(("res", l, x, x1, gn1, h, gn2, film))
+        return out
 
     def _attn(self, l: _Attn, x):
         dt, w = self.dt, self.w
@@ -266,22 +271,6 @@ class AdmEngine:
         a = ops.attention(qkv.view(n, hh * ww, 3 * c), l.heads, 1 if self.cfg.use_new_attention_order else 0, dt)
         out = ops.igemm(a.view(n * hh * ww, c), w[l.p + ".proj"], residual=x.view(n * hh * ww, c), want_stats=True, hw=hh * ww)
         return ops.view_nhwc(out, n, hh, ww)
-
-    def _run(self, layers, h, h1, emb):
-        for l in layers:
-            if isinstance(l, tuple):
-                h = ops.igemm(h, self.w[l[1]], want_stats=True)
-            elif isinstance(l, _Res):
-                h = self._res(l, h, h1, emb)
-            elif isinstance(l, _Attn):
-                h = self._attn(l, h)
-            elif isinstance(l, _Resample):
-                if self.cfg.conv_resample:
-                    h = ops.igemm(h, self.w[l.p], up=l.up, stride=1 if l.up else 2, want_stats=True)
-                else:
-                    raise NotImplementedError("conv_resample=False is not used by the shipped configs")
-            h1 = None
-        return h
 
     def _embed_input(self, images, timesteps):
         """Time embedding (all emb_layers outputs at once) and the padded NHWC input x = 2 * images - 1: (emb, x)."""
@@ -315,17 +304,49 @@ class AdmEngine:
         call("pmi_finish_output", ptr(y), y.shape[-1], ptr(out), n, hh, ww, co)
         return out
 
+    def _run(self, layers, h, h1, emb, tape=None, sd=None):
+        """One layer list of the plan on h (and the skip tensor h1 its first block concatenates).  With a tape (training mode; sd: the state
+        dict, for the attention's repacked qkv) every layer appends its record for _back."""
+        for l in layers:
+            if isinstance(l, tuple):
+                if tape is not None:
+                    tape.append(("conv", l, h))
+                h = ops.igemm(h, self.w[l[1]], want_stats=True)
+            elif isinstance(l, _Res):
+                h = self._res(l, h, h1, emb, tape)
+            elif isinstance(l, _Attn):
+                h = self._attn(l, h) if tape is None else self._attn_train(l, h, tape, sd)
+            elif isinstance(l, _Resample):                # unet.py:81-138: nearest x2 + conv / stride-2 conv
+                if not self.cfg.conv_resample:
+                    raise NotImplementedError("conv_resample=False is not used by the shipped configs")
+                h = ops.igemm(h, self.w[l.p], up=l.up, stride=1 if l.up else 2, want_stats=True)
+                if tape is not None:
+                    tape.append(("resample", l))
+            h1 = None
+        return h
+
+    def _unet(self, emb, h, tape=None, sd=None):
+        """The U over inp / mid / out -> the input of the output norm.  tape: {"inp": [], "mid": [], "out": []}, filled with one list of
+        records per layer list (mid: the records themselves)."""
+        def sub(key):
+            if tape is None:
+                return None
+            tape[key].append([])
+            return tape[key][-1]
+        hs = []
+        for layers in self.inp:
+            h = self._run(layers, h, None, emb, sub("inp"), sd)
+            hs.append(h)
+        h = self._run(self.mid, h, None, emb, None if tape is None else tape["mid"], sd)
+        for layers in self.out:
+            h = self._run(layers, h, hs.pop(), emb, sub("out"), sd)
+        return h
+
     @torch.no_grad()
     def forward(self, images: torch.Tensor, timesteps: torch.Tensor, out_channels: Optional[int] = None) -> torch.Tensor:
         """images: NCHW fp32 in [0,1] (encoded to x = 2*img-1 on the fly); returns NCHW fp32 model output."""
         emb, h = self._embed_input(images, timesteps)
-        hs = []
-        for layers in self.inp:
-            h = self._run(layers, h, None, emb)
-            hs.append(h)
-        h = self._run(self.mid, h, None, emb)
-        for layers in self.out:
-            h = self._run(layers, h, hs.pop(), emb)
+        h = self._unet(emb, h)
         ca, cb = ops.group_norm_coeffs(h, *self.gn_out, 32, self.dt)
         return self._output(h, ca, cb, out_channels)
 
@@ -353,31 +374,6 @@ class AdmEngine:
             self.w[key + ".w"] = wq
         return self.w[key], self.w[key + ".w"]
 
-    def _res_train(self, l: _Res, x, x1, emb, tape):
-        cfg, dt, w = self.cfg, self.dt, self.w
-        g1, b1 = w[l.p + ".gn1"]
-        ecols = 2 * l.cout if cfg.use_scale_shift_norm else l.cout
-        e = emb[:, l.emb_off:l.emb_off + ecols]
-        nb = None if cfg.use_scale_shift_norm else e
-        ca, cb, parts = ops.group_norm_coeffs_train(x, g1, b1, 32, dt, x1=x1)
-        skip, skip1 = x, x1
-        if l.down:
-            if x1 is not None:
-                raise NotImplementedError("down-sampling ResBlock over a concatenated input does not occur in the shipped configs")
-            n, hh, ww, c = x.shape
-            hp = torch.empty((n, hh // 2, ww // 2, c), dtype=x.dtype, device=x.device)
-            skip = torch.empty_like(hp)
-            call("pmi_gn_apply_pool_skip", ptr(x), ptr(ca), ptr(cb), ptr(hp), ptr(skip), n, hh, ww, ops.logical_c(x, dt), ACT_SILU, dt)
-            h = ops.igemm(hp, w[l.p + ".conv1"], nbias=nb, want_stats=True)
-        else:
-            h = ops.igemm(x, w[l.p + ".conv1"], a1=x1, up=l.up, nbias=nb, prologue=(ca, cb, ACT_SILU), want_stats=True)
-        g2, b2 = w[l.p + ".gn2"]
-        film = e if cfg.use_scale_shift_norm else None
-        ca2, cb2, parts2 = ops.group_norm_coeffs_train(h, g2, b2, 32, dt, film=film, film_ld=emb.stride(0) if film is not None else 0)
-        out = self._conv2(l, h, skip, skip1, (ca2, cb2, ACT_SILU))
-        tape.append(("res", l, x, x1, (ca, cb, parts), h, (ca2, cb2, parts2), film))
-        return out
-
     def _attn_train(self, l: _Attn, x, tape, sd):
         dt, w = self.dt, self.w
         n, hh, ww, c = x.shape
@@ -393,45 +389,15 @@ class AdmEngine:
         tape.append(("attn", l, x, (ca, cb, parts), saved))
         return ops.view_nhwc(out, n, hh, ww)
 
-    def _run_train(self, layers, h, h1, emb, tape, sd):
-        for l in layers:
-            if isinstance(l, tuple):
-                x_in = h
-                h = ops.igemm(h, self.w[l[1]], want_stats=True)
-                tape.append(("conv", l, x_in))
-            elif isinstance(l, _Res):
-                h = self._res_train(l, h, h1, emb, tape)
-            elif isinstance(l, _Attn):
-                h = self._attn_train(l, h, tape, sd)
-            elif isinstance(l, _Resample) and self.cfg.conv_resample:      # unet.py:81-138: nearest x2 + conv / stride-2 conv
-                h = ops.igemm(h, self.w[l.p], up=l.up, stride=1 if l.up else 2, want_stats=True)
-                tape.append(("resample", l))
-            else:
-                raise NotImplementedError("conv_resample=False is not used by the shipped configs")
-            h1 = None
-        return h
-
     @torch.no_grad()
     def forward_train(self, images: torch.Tensor, timesteps: torch.Tensor, state_dict, out_channels: Optional[int] = None):
         """As forward(), keeping what backward() needs.  Returns (model output NCHW fp32, tape)."""
         emb, h = self._embed_input(images, timesteps)
-        sd = state_dict
-        tape = {"inp": [], "mid": [], "out": []}
-        hs = []
-        for layers in self.inp:
-            tp = []
-            h = self._run_train(layers, h, None, emb, tp, sd)
-            tape["inp"].append(tp)
-            hs.append(h)
-        h = self._run_train(self.mid, h, None, emb, tape["mid"], sd)
-        for layers in self.out:
-            tp = []
-            h = self._run_train(layers, h, hs.pop(), emb, tp, sd)
-            tape["out"].append(tp)
-        ca, cb, parts = ops.group_norm_coeffs_train(h, *self.gn_out, 32, self.dt)
-        tape["last"] = (h, (ca, cb, parts))
-        tape["emb_ld"] = emb.stride(0)
-        return self._output(h, ca, cb, out_channels), tape
+        tape = {"inp": [], "mid": [], "out": [], "emb_ld": emb.stride(0)}
+        h = self._unet(emb, h, tape, state_dict)
+        gn = ops.group_norm_coeffs_train(h, *self.gn_out, 32, self.dt)
+        tape["last"] = (h, gn)
+        return self._output(h, gn[0], gn[1], out_channels), tape
 
     def _resample_bwd(self, l: _Res, g):
         """Gradient through the block's resampling of a path (nearest x2 up / 2x2 average down)."""

@@ -187,7 +187,8 @@ class AdmMixedEngine(AdmEngine):
         finally:
             self.dt = DT_F16X2
 
-    def _run(self, layers, h, h1, emb):
+    def _run(self, layers, h, h1, emb, tape=None, sd=None):
+        assert tape is None          # (AdmEngine._run's signature: forward_train raises above, so no tape reaches here)
         for l in layers:
             if isinstance(l, tuple):
                 h = ops.igemm(h, self.w[l[1]], want_stats=True)

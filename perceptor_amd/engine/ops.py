@@ -731,29 +731,6 @@ def bgemm(A: torch.Tensor, B: torch.Tensor, D: torch.Tensor, *, M: int, N: int, 
     return D
 
 
-def _gn_coeffs(x, x1, gamma, beta, groups, dt, film, film_ld, eps):
-    n, h, w, _ = x.shape
-    c0 = logical_c(x, dt)
-    c1 = logical_c(x1, dt) if x1 is not None else 0
-    c, hw, dev = c0 + c1, h * w, x.device
-    ca = _empty((n, c), torch.float32, dev)
-    cb = _empty((n, c), torch.float32, dev)
-    st0 = getattr(x, "_pmi_stats", None)
-    st1 = getattr(x1, "_pmi_stats", None) if x1 is not None else None
-    if st0 is not None and (x1 is None or st1 is not None):
-        # statistics came out of the producing kernels' epilogues: no pass over the activations at all
-        call("pmi_gn_finalize", ptr(st0[0]), st0[1], c0, ptr(st1[0]) if st1 else None, st1[1] if st1 else 0, c1,
-             ptr(gamma), ptr(beta), ptr(film), film_ld, ptr(ca), ptr(cb), n, hw, groups, eps)
-        return ca, cb
-    # pixel chunks per sample: ~1024 workgroups per launch, at least 8 pixels each (64 left a 16x16 map at batch 8 with 32 workgroups whose
-    # threads walked 64 pixels one dependent load after the other: 27 us per launch)
-    nchunk = max(1, min(hw // 8, (1024 + n - 1) // n))
-    ws = _empty((n, nchunk, c, 2), torch.float32, dev)
-    call("pmi_gn_stats", ptr(x), ptr(x1), c0, ptr(ws), n, hw, c, groups, nchunk, dt)
-    call("pmi_gn_finalize", ptr(ws), nchunk, c, None, 0, 0, ptr(gamma), ptr(beta), ptr(film), film_ld, ptr(ca), ptr(cb), n, hw, groups, eps)
-    return ca, cb
-
-
 def group_norm_coeffs_train(x: torch.Tensor, gamma, beta, groups: int, dt: int, *, x1: Optional[torch.Tensor] = None,
                             film: Optional[torch.Tensor] = None, film_ld: int = 0, eps: float = 1e-5):
     """As group_norm_coeffs, also returning the per-channel (sum, sumsq) partials the coefficients came from, as the argument tuple
@@ -766,8 +743,11 @@ def group_norm_coeffs_train(x: torch.Tensor, gamma, beta, groups: int, dt: int, 
     st0 = getattr(x, "_pmi_stats", None)
     st1 = getattr(x1, "_pmi_stats", None) if x1 is not None else None
     if st0 is not None and (x1 is None or st1 is not None):
+        # statistics came out of the producing kernels' epilogues: no pass over the activations at all
         parts = (st0[0], st0[1], c0, st1[0] if st1 else None, st1[1] if st1 else 0, c1)
     else:
+        # pixel chunks per sample: ~1024 workgroups per launch, at least 8 pixels each (64 left a 16x16 map at batch 8 with 32 workgroups whose
+        # threads walked 64 pixels one dependent load after the other: 27 us per launch)
         nchunk = max(1, min(hw // 8, (1024 + n - 1) // n))
         ws = _empty((n, nchunk, c, 2), torch.float32, dev)
         call("pmi_gn_stats", ptr(x), ptr(x1), c0, ptr(ws), n, hw, c, groups, nchunk, dt)
@@ -812,7 +792,7 @@ def group_norm_backward(x: torch.Tensor, dy: torch.Tensor, ca, cb, parts, gamma,
 def group_norm_coeffs(x: torch.Tensor, gamma, beta, groups: int, dt: int, *, x1: Optional[torch.Tensor] = None,
                       film: Optional[torch.Tensor] = None, film_ld: int = 0, eps: float = 1e-5):
     """Per-(sample, channel) coefficients (a, b) with norm(x)*gamma+beta[FiLM] = x*a+b (no apply pass)."""
-    return _gn_coeffs(x, x1, gamma, beta, groups, dt, film, film_ld, eps)
+    return group_norm_coeffs_train(x, gamma, beta, groups, dt, x1=x1, film=film, film_ld=film_ld, eps=eps)[:2]
 
 
 def group_norm(x: torch.Tensor, gamma, beta, groups: int, dt: int, *, x1: Optional[torch.Tensor] = None,
@@ -822,22 +802,27 @@ def group_norm(x: torch.Tensor, gamma, beta, groups: int, dt: int, *, x1: Option
     n, h, w, _ = x.shape
     c0 = logical_c(x, dt)
     c = c0 + (logical_c(x1, dt) if x1 is not None else 0)
-    ca, cb = _gn_coeffs(x, x1, gamma, beta, groups, dt, film, film_ld, eps)
+    ca, cb = group_norm_coeffs(x, gamma, beta, groups, dt, x1=x1, film=film, film_ld=film_ld, eps=eps)
     cphys = 2 * c if dt == DT_F16X2 else c
     y = _empty((n, h // 2, w // 2, cphys) if pool else (n, h, w, cphys), x.dtype, x.device)
     call("pmi_gn_apply", ptr(x), ptr(x1), c0, ptr(ca), ptr(cb), ptr(residual), ptr(y), n, h, w, c, act, int(pool), dt)
     return y
 
 
-def group_norm_pool_skip(x: torch.Tensor, gamma, beta, groups: int, dt: int, act: int = ACT_NONE, eps: float = 1e-5):
-    """(AvgPool2d(2)(act(GroupNorm(x))), AvgPool2d(2)(x)) from one pass over x: both inputs of a down ResBlock (unet.py:232-243)."""
+def group_norm_pool_skip_train(x: torch.Tensor, gamma, beta, groups: int, dt: int, act: int = ACT_NONE, eps: float = 1e-5):
+    """As group_norm_pool_skip, also returning the norm's (ca, cb, parts) of group_norm_coeffs_train."""
     n, h, w, _ = x.shape
     c = logical_c(x, dt)
-    ca, cb = _gn_coeffs(x, None, gamma, beta, groups, dt, None, 0, eps)
+    gn = group_norm_coeffs_train(x, gamma, beta, groups, dt, eps=eps)
     y = _empty((n, h // 2, w // 2, x.shape[-1]), x.dtype, x.device)
     y_raw = _empty((n, h // 2, w // 2, x.shape[-1]), x.dtype, x.device)
-    call("pmi_gn_apply_pool_skip", ptr(x), ptr(ca), ptr(cb), ptr(y), ptr(y_raw), n, h, w, c, act, dt)
-    return y, y_raw
+    call("pmi_gn_apply_pool_skip", ptr(x), ptr(gn[0]), ptr(gn[1]), ptr(y), ptr(y_raw), n, h, w, c, act, dt)
+    return y, y_raw, gn
+
+
+def group_norm_pool_skip(x: torch.Tensor, gamma, beta, groups: int, dt: int, act: int = ACT_NONE, eps: float = 1e-5):
+    """(AvgPool2d(2)(act(GroupNorm(x))), AvgPool2d(2)(x)) from one pass over x: both inputs of a down ResBlock (unet.py:232-243)."""
+    return group_norm_pool_skip_train(x, gamma, beta, groups, dt, act, eps)[:2]
 
 
 def avgpool2(x: torch.Tensor, dt: int) -> torch.Tensor:

@@ -299,14 +299,36 @@ class _Blocks:
         if k + ".conv_shortcut.weight" in self.sd:
             w[k + ".skip"] = self._lin(k + ".conv_shortcut", sources=srcs)
 
-    def _resnet(self, k, x, x1, nbias, groups, eps):
+    def _resnet(self, k, x, x1, nbias, groups, eps, tape=None):
+        """ResnetBlock2D on x (and the skip tensor x1 it concatenates).  Inference and training mode issue the same launches: with a tape,
+        the block's record for _res_back (its inputs, both norms' coefficients and partials, conv1's output) is appended to it."""
         dt, w = self.dt, self.w
-        ca, cb = ops.group_norm_coeffs(x, *w[k + ".gn1"], groups, dt, x1=x1, eps=eps)
-        h = ops.igemm(x, w[k + ".conv1"], a1=x1, nbias=nbias, prologue=(ca, cb, ACT_SILU), want_stats=True)
-        ca, cb = ops.group_norm_coeffs(h, *w[k + ".gn2"], groups, dt, eps=eps)
+        gn1 = ops.group_norm_coeffs_train(x, *w[k + ".gn1"], groups, dt, x1=x1, eps=eps)
+        h = ops.igemm(x, w[k + ".conv1"], a1=x1, nbias=nbias, prologue=(gn1[0], gn1[1], ACT_SILU), want_stats=True)
+        gn2 = ops.group_norm_coeffs_train(h, *w[k + ".gn2"], groups, dt, eps=eps)
         skip = ops.igemm(x, w[k + ".skip"], a1=x1) if (k + ".skip") in w else x
         assert (k + ".skip") in w or x1 is None
-        return ops.igemm(h, w[k + ".conv2"], residual=skip, prologue=(ca, cb, ACT_SILU), want_stats=True)
+        if tape is not None:
+            tape.append(("res", k, x, x1, gn1, h, gn2))
+        return ops.igemm(h, w[k + ".conv2"], residual=skip, prologue=(gn2[0], gn2[1], ACT_SILU), want_stats=True)
+
+    def _res_back(self, rec, g, sd, groups, eps):
+        """(gradient wrt x, wrt x1 or None) of the ResnetBlock2D recorded in `rec` from g = gradient wrt its output."""
+        _, k, x, x1, gn1, h, gn2 = rec
+        dt, w, dev = self.dt, self.w, self.device
+        d_a2 = ops.igemm(g, ops.packed_dx(w, k + ".conv2T", sd[k + ".conv2.weight"], dt, dev))                  # wrt SiLU(GN2(h))
+        dh, _ = ops.group_norm_backward(h, d_a2, *gn2, w[k + ".gn2"][0], groups, dt, act=ACT_SILU, eps=eps)
+        d_a1 = ops.igemm(dh, ops.packed_dx(w, k + ".conv1T", sd[k + ".conv1.weight"], dt, dev))                 # wrt SiLU(GN1(cat(x, x1)))
+        gs0, gs1 = g, None
+        if (k + ".skip") in w:
+            skw = sd[k + ".conv_shortcut.weight"]
+            if x1 is None:
+                gs0 = ops.igemm(g, ops.packed_dx(w, k + ".skipT", skw, dt, dev))
+            else:
+                c0 = x.shape[-1]
+                gs0 = ops.igemm(g, ops.packed_dx(w, k + ".skipT0", skw[:, :c0], dt, dev))
+                gs1 = ops.igemm(g, ops.packed_dx(w, k + ".skipT1", skw[:, c0:], dt, dev))
+        return ops.group_norm_backward(x, d_a1, *gn1, w[k + ".gn1"][0], groups, dt, x1=x1, act=ACT_SILU, gadd0=gs0, gadd1=gs1, eps=eps)
 
     def _up_back(self, k, g, sd):
         """Gradient wrt the input of nearest-x2 + conv3x3 from g = gradient wrt its output [N, 2h, 2w, C]: one stride-2 pass on the
@@ -334,17 +356,8 @@ class _Blocks:
         return ops.view_nhwc(o, n, h2, w2)
 
 
-    # ---- what the VAE decoder's and encoder's input gradients share: the tape-keeping forms of the ResnetBlock2D and the mid attention, and
-    # their backward steps (see VaeDecoderEngine) ----------------------------------------------------------------------------------------
-    def _vae_resnet_train(self, k, x, tape, groups, eps):
-        dt, w = self.dt, self.w
-        ca, cb, p1 = ops.group_norm_coeffs_train(x, *w[k + ".gn1"], groups, dt, eps=eps)
-        h = ops.igemm(x, w[k + ".conv1"], prologue=(ca, cb, ACT_SILU), want_stats=True)
-        ca2, cb2, p2 = ops.group_norm_coeffs_train(h, *w[k + ".gn2"], groups, dt, eps=eps)
-        skip = ops.igemm(x, w[k + ".skip"]) if (k + ".skip") in w else x
-        tape.append(("res", k, x, (ca, cb, p1), h, (ca2, cb2, p2)))
-        return ops.igemm(h, w[k + ".conv2"], residual=skip, prologue=(ca2, cb2, ACT_SILU), want_stats=True)
-
+    # ---- what the VAE decoder's and encoder's input gradients share: the tape-keeping form of the mid attention (other kernels than
+    # _vae_attention: the softmax P is kept) and the backward steps (see VaeDecoderEngine) -------------------------------------------------
     def _vae_attention_train(self, a, x, tape, groups):
         dt, w = self.dt, self.w
         n, h2, w2, cc = x.shape
@@ -357,16 +370,6 @@ class _Blocks:
         o = ops.igemm(at.view(m, cc), w[a + ".proj"], residual=x.view(m, cc), want_stats=True, hw=h2 * w2)
         tape.append(("attn", a, x, (ca, cb, parts), qkv, pm))
         return ops.view_nhwc(o, n, h2, w2)
-
-    def _vae_res_back(self, rec, g, sd, groups, eps):
-        _, k, x, gn1, h, gn2 = rec
-        dt, w, dev = self.dt, self.w, self.device
-        d_a2 = ops.igemm(g, ops.packed_dx(w, k + ".conv2T", sd[k + ".conv2.weight"], dt, dev))                  # wrt SiLU(GN2(h))
-        dh, _ = ops.group_norm_backward(h, d_a2, *gn2, w[k + ".gn2"][0], groups, dt, act=ACT_SILU, eps=eps)
-        d_a1 = ops.igemm(dh, ops.packed_dx(w, k + ".conv1T", sd[k + ".conv1.weight"], dt, dev))                 # wrt SiLU(GN1(x))
-        gs = ops.igemm(g, ops.packed_dx(w, k + ".skipT", sd[k + ".conv_shortcut.weight"], dt, dev)) if (k + ".skip") in w else g
-        gx, _ = ops.group_norm_backward(x, d_a1, *gn1, w[k + ".gn1"][0], groups, dt, act=ACT_SILU, gadd0=gs, eps=eps)
-        return gx
 
     def _vae_attn_back(self, rec, g, sd, groups):
         _, a, x, gn, qkv, pm = rec
@@ -466,18 +469,37 @@ class SdUnetEngine(_Blocks):
         out = ops.igemm(h16, w[k + ".proj_out"], residual=x.view(m, c), want_stats=True, hw=t)
         return ops.view_nhwc(out, n, hh, ww)
 
-    def _run(self, blk, h, h1, emb, kv_all, tc):
+    def _run(self, blk, h, h1, emb, kv_all, tc, tape=None):
+        """One block of the plan on h (and the skip tensor h1 its first ResnetBlock2D concatenates).  With a tape (training mode) every layer
+        appends its record for _back."""
         for l in blk:
             if l[0] == "res":
                 off, co = self.emb_off[l[1]]
-                h = self._resnet(l[1], h, h1, emb[:, off:off + co], self.cfg.groups, 1e-5)
+                h = self._resnet(l[1], h, h1, emb[:, off:off + co], self.cfg.groups, 1e-5, tape)
             elif l[0] == "attn":
-                h = self._attn(l[1], h, kv_all, tc)
-            elif l[0] == "down":
-                h = ops.igemm(h, self.w[l[1]], stride=2, want_stats=True)
+                h = self._attn(l[1], h, kv_all, tc) if tape is None else self._attn_train(l[1], h, kv_all, tc, tape)
             else:
-                h = ops.igemm(h, self.w[l[1]], up=True, want_stats=True)
+                if tape is not None:
+                    tape.append((l[0], l[1]))
+                h = ops.igemm(h, self.w[l[1]], stride=2, want_stats=True) if l[0] == "down" else ops.igemm(h, self.w[l[1]], up=True, want_stats=True)
             h1 = None
+        return h
+
+    def _unet(self, emb, kv_all, tc, h, tape=None):
+        """The U over down / mid / up from conv_in's output -> the input of the output norm.  tape: {"down": [], "mid": [], "up": []}, filled
+        with one list of records per block (mid: the records themselves)."""
+        def sub(key):
+            if tape is None:
+                return None
+            tape[key].append([])
+            return tape[key][-1]
+        hs = [h]
+        for blk in self.down:
+            h = self._run(blk, h, None, emb, kv_all, tc, sub("down"))
+            hs.append(h)
+        h = self._run(self.mid, h, None, emb, kv_all, tc, None if tape is None else tape["mid"])
+        for blk in self.up:
+            h = self._run(blk, h, hs.pop(), emb, kv_all, tc, sub("up"))
         return h
 
     def _inputs(self, latents, timesteps, context):
@@ -517,13 +539,7 @@ class SdUnetEngine(_Blocks):
     def forward(self, latents: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor) -> torch.Tensor:
         """latents NCHW fp32 [N, in, h, w], timesteps [N], context [N, T, context_dim] fp32 -> predicted noise NCHW fp32."""
         emb, kv_all, tc, h = self._inputs(latents, timesteps, context)
-        hs = [h]
-        for blk in self.down:
-            h = self._run(blk, h, None, emb, kv_all, tc)
-            hs.append(h)
-        h = self._run(self.mid, h, None, emb, kv_all, tc)
-        for blk in self.up:
-            h = self._run(blk, h, hs.pop(), emb, kv_all, tc)
+        h = self._unet(emb, kv_all, tc, h)
         ca, cb = ops.group_norm_coeffs(h, *self.gn_out, self.cfg.groups, self.dt)
         return self._output(h, ca, cb)
 
@@ -546,16 +562,6 @@ class SdUnetEngine(_Blocks):
         mr = torch.empty((2, m), dtype=torch.float32, device=x32.device)
         call("pmi_layernorm_fwd", ptr(x32), c, ptr(gb[0]), ptr(gb[1]), ptr(y), None, ptr(mr), m, c, 1e-5, self.dt)
         return y, mr
-
-    def _resnet_train(self, k, x, x1, nbias, tape):
-        dt, w, groups = self.dt, self.w, self.cfg.groups
-        ca, cb, p1 = ops.group_norm_coeffs_train(x, *w[k + ".gn1"], groups, dt, x1=x1)
-        h = ops.igemm(x, w[k + ".conv1"], a1=x1, nbias=nbias, prologue=(ca, cb, ACT_SILU), want_stats=True)
-        ca2, cb2, p2 = ops.group_norm_coeffs_train(h, *w[k + ".gn2"], groups, dt)
-        skip = ops.igemm(x, w[k + ".skip"], a1=x1) if (k + ".skip") in w else x
-        assert (k + ".skip") in w or x1 is None
-        tape.append(("res", k, x, x1, (ca, cb, p1), h, (ca2, cb2, p2)))
-        return ops.igemm(h, w[k + ".conv2"], residual=skip, prologue=(ca2, cb2, ACT_SILU), want_stats=True)
 
     def _attn_train(self, k, x, kv_all, tc, tape):
         dt, w, heads = self.dt, self.w, self.cfg.heads
@@ -593,60 +599,17 @@ class SdUnetEngine(_Blocks):
         tape.append(("attn", k, x, (ca, cb, parts), (h0, mr1, s1), (h1, mr2, s2), (h2, mr3, f), flash))
         return ops.view_nhwc(out, n, hh, ww)
 
-    def _run_train(self, blk, h, h1, emb, kv_all, tc, tape):
-        for l in blk:
-            if l[0] == "res":
-                off, co = self.emb_off[l[1]]
-                h = self._resnet_train(l[1], h, h1, emb[:, off:off + co], tape)
-            elif l[0] == "attn":
-                h = self._attn_train(l[1], h, kv_all, tc, tape)
-            elif l[0] == "down":
-                tape.append(("down", l[1]))
-                h = ops.igemm(h, self.w[l[1]], stride=2, want_stats=True)
-            else:
-                tape.append(("up", l[1]))
-                h = ops.igemm(h, self.w[l[1]], up=True, want_stats=True)
-            h1 = None
-        return h
-
     @torch.no_grad()
     def forward_train(self, latents: torch.Tensor, timesteps: torch.Tensor, context: torch.Tensor):
         """As forward(), keeping what backward() needs: (predicted noise NCHW fp32, tape)."""
         emb, kv_all, tc, h = self._inputs(latents, timesteps, context)
         tape = {"down": [], "mid": [], "up": [], "in_shape": tuple(latents.shape), "ctx_shape": tuple(context.shape)}
-        hs = [h]
-        for blk in self.down:
-            tp = []
-            h = self._run_train(blk, h, None, emb, kv_all, tc, tp)
-            tape["down"].append(tp)
-            hs.append(h)
-        h = self._run_train(self.mid, h, None, emb, kv_all, tc, tape["mid"])
-        for blk in self.up:
-            tp = []
-            h = self._run_train(blk, h, hs.pop(), emb, kv_all, tc, tp)
-            tape["up"].append(tp)
-        ca, cb, parts = ops.group_norm_coeffs_train(h, *self.gn_out, self.cfg.groups, self.dt)
-        tape["last"] = (h, (ca, cb, parts))
-        out = self._output(h, ca, cb)
+        h = self._unet(emb, kv_all, tc, h, tape)
+        gn = ops.group_norm_coeffs_train(h, *self.gn_out, self.cfg.groups, self.dt)
+        tape["last"] = (h, gn)
+        out = self._output(h, gn[0], gn[1])
         tape["out_shape"] = tuple(out.shape)
         return out, tape
-
-    def _res_back(self, rec, g, sd):
-        _, k, x, x1, gn1, h, gn2 = rec
-        dt, w, dev, groups = self.dt, self.w, self.device, self.cfg.groups
-        d_a2 = ops.igemm(g, ops.packed_dx(w, k + ".conv2T", sd[k + ".conv2.weight"], dt, dev))                  # wrt SiLU(GN2(h))
-        dh, _ = ops.group_norm_backward(h, d_a2, *gn2, w[k + ".gn2"][0], groups, dt, act=ACT_SILU)
-        d_a1 = ops.igemm(dh, ops.packed_dx(w, k + ".conv1T", sd[k + ".conv1.weight"], dt, dev))                 # wrt SiLU(GN1(cat(x, x1)))
-        gs0, gs1 = g, None
-        if (k + ".skip") in w:
-            skw = sd[k + ".conv_shortcut.weight"]
-            if x1 is None:
-                gs0 = ops.igemm(g, ops.packed_dx(w, k + ".skipT", skw, dt, dev))
-            else:
-                c0 = x.shape[-1]
-                gs0 = ops.igemm(g, ops.packed_dx(w, k + ".skipT0", skw[:, :c0], dt, dev))
-                gs1 = ops.igemm(g, ops.packed_dx(w, k + ".skipT1", skw[:, c0:], dt, dev))
-        return ops.group_norm_backward(x, d_a1, *gn1, w[k + ".gn1"][0], groups, dt, x1=x1, act=ACT_SILU, gadd0=gs0, gadd1=gs1)
 
     def _ln_back(self, dy32, x32, gb, mr, gres, m, c):
         """(fp32, 16-bit) gradient wrt the token stream in front of a LayerNorm: LayerNorm backward of dy32 plus gres, the gradient that
@@ -719,7 +682,7 @@ class SdUnetEngine(_Blocks):
         for rec in reversed(tp):
             assert g1 is None
             if rec[0] == "res":
-                g, g1 = self._res_back(rec, g, sd)
+                g, g1 = self._res_back(rec, g, sd, self.cfg.groups, 1e-5)
             elif rec[0] == "attn":
                 g = self._attn_back(rec, g, sd, cg)
             elif rec[0] == "up":
@@ -818,18 +781,27 @@ class VaeDecoderEngine(_Blocks):
         call("pmi_nhwc_to_nchw", ptr(y), y.shape[-1], ptr(out), n, ho, wo, self.cfg.out_channels, mul, add)
         return out
 
+    def _blocks(self, h, rec=None):
+        """The mid block and the up blocks from conv_in's output -> the input of the output norm.  With rec (training mode) every layer appends
+        its record for backward()."""
+        g, eps, a = self.cfg.groups, 1e-6, "decoder.mid_block.attentions.0"
+        h = self._resnet("decoder.mid_block.resnets.0", h, None, None, g, eps, rec)
+        h = self._vae_attention(a, h, g) if rec is None else self._vae_attention_train(a, h, rec, g)
+        h = self._resnet("decoder.mid_block.resnets.1", h, None, None, g, eps, rec)
+        for kind, k in self.plan:
+            if kind == "res":
+                h = self._resnet(k, h, None, None, g, eps, rec)
+            else:
+                if rec is not None:
+                    rec.append(("up", k))
+                h = ops.igemm(h, self.w[k], up=True, want_stats=True)
+        return h
+
     @torch.no_grad()
     def forward(self, latents: torch.Tensor, scale: float = 1.0 / 0.18215, to_images: bool = True) -> torch.Tensor:
         """latents NCHW fp32 (the UNet's space) -> images NCHW fp32 in [0, 1] (to_images) or the decoder's x in [-1, 1]."""
-        cfg, dt, w = self.cfg, self.dt, self.w
-        h = self._conv_in(latents, scale)
-        g, eps = cfg.groups, 1e-6
-        h = self._resnet("decoder.mid_block.resnets.0", h, None, None, g, eps)
-        h4 = self._vae_attention("decoder.mid_block.attentions.0", h, g)
-        h = self._resnet("decoder.mid_block.resnets.1", h4, None, None, g, eps)
-        for kind, k in self.plan:
-            h = self._resnet(k, h, None, None, g, eps) if kind == "res" else ops.igemm(h, w[k], up=True, want_stats=True)
-        ca, cb = ops.group_norm_coeffs(h, *self.gn_out, g, dt, eps=eps)
+        h = self._blocks(self._conv_in(latents, scale))
+        ca, cb = ops.group_norm_coeffs(h, *self.gn_out, self.cfg.groups, self.dt, eps=1e-6)
         return self._output(h, ca, cb, to_images)
 
     # ---- input gradient (d loss / d latents through the frozen decoder: loss-guided sampling) -----------------------------------------
@@ -843,22 +815,11 @@ class VaeDecoderEngine(_Blocks):
     def forward_train(self, latents: torch.Tensor, scale: float = 1.0 / 0.18215, to_images: bool = True):
         """As forward(), keeping what backward() needs: (images NCHW fp32, tape).  For head dims above 160 (SD-v1: 512) the value equals
         forward()'s bit for bit; a 64-channel head runs forward()'s d64 kernel there and the batched GEMMs here (rounding-level)."""
-        cfg, dt, w = self.cfg, self.dt, self.w
-        h = self._conv_in(latents, scale)
-        g, eps = cfg.groups, 1e-6
         rec: List[tuple] = []
-        h = self._vae_resnet_train("decoder.mid_block.resnets.0", h, rec, g, eps)
-        h = self._vae_attention_train("decoder.mid_block.attentions.0", h, rec, g)
-        h = self._vae_resnet_train("decoder.mid_block.resnets.1", h, rec, g, eps)
-        for kind, k in self.plan:
-            if kind == "res":
-                h = self._vae_resnet_train(k, h, rec, g, eps)
-            else:
-                rec.append(("up", k))
-                h = ops.igemm(h, w[k], up=True, want_stats=True)
-        ca, cb, parts = ops.group_norm_coeffs_train(h, *self.gn_out, g, dt, eps=eps)
-        out = self._output(h, ca, cb, to_images)
-        tape = {"rec": rec, "last": (h, (ca, cb, parts)), "scale": float(scale), "to_images": bool(to_images),
+        h = self._blocks(self._conv_in(latents, scale), rec)
+        gn = ops.group_norm_coeffs_train(h, *self.gn_out, self.cfg.groups, self.dt, eps=1e-6)
+        out = self._output(h, gn[0], gn[1], to_images)
+        tape = {"rec": rec, "last": (h, gn), "scale": float(scale), "to_images": bool(to_images),
                 "in_shape": tuple(latents.shape), "out_shape": tuple(out.shape)}
         return out, tape
 
@@ -881,7 +842,7 @@ class VaeDecoderEngine(_Blocks):
         g, _ = ops.group_norm_backward(h, d_act, *gn, self.gn_out[0], g_, dt, act=ACT_SILU, eps=eps)
         for rec in reversed(tape["rec"]):
             if rec[0] == "res":
-                g = self._vae_res_back(rec, g, sd, g_, eps)
+                g, _ = self._res_back(rec, g, sd, g_, eps)
             elif rec[0] == "attn":
                 g = self._vae_attn_back(rec, g, sd, g_)
             else:
@@ -951,46 +912,43 @@ class VaeEncoderEngine(_Blocks):
         lc = self.cfg.latent_channels
         return out[:, :lc].contiguous(), out[:, lc:2 * lc].contiguous()
 
+    def _blocks(self, h, rec=None):
+        """The down blocks and the mid block from conv_in's output -> the input of the output norm.  With rec (training mode) every layer
+        appends its record for backward()."""
+        g, eps, a = self.cfg.groups, 1e-6, "encoder.mid_block.attentions.0"
+        for kind, k in self.plan:
+            if kind == "res":
+                h = self._resnet(k, h, None, None, g, eps, rec)
+            else:
+                if rec is not None:
+                    rec.append(("down", k))
+                h = self._down(h, self.w[k])
+        h = self._resnet("encoder.mid_block.resnets.0", h, None, None, g, eps, rec)
+        h = self._vae_attention(a, h, g) if rec is None else self._vae_attention_train(a, h, rec, g)
+        return self._resnet("encoder.mid_block.resnets.1", h, None, None, g, eps, rec)
+
     @torch.no_grad()
     def forward(self, images: torch.Tensor):
         """images NCHW fp32 in [0, 1] -> (mean, logvar) NCHW fp32 [N, latent, H/8, W/8] of the latent distribution."""
-        cfg, dt, w = self.cfg, self.dt, self.w
-        h = self._conv_in(images)
-        g, eps = cfg.groups, 1e-6
-        for kind, k in self.plan:
-            h = self._resnet(k, h, None, None, g, eps) if kind == "res" else self._down(h, w[k])
-        h = self._resnet("encoder.mid_block.resnets.0", h, None, None, g, eps)
-        h = self._vae_attention("encoder.mid_block.attentions.0", h, g)
-        h = self._resnet("encoder.mid_block.resnets.1", h, None, None, g, eps)
-        ca, cb = ops.group_norm_coeffs(h, *self.gn_out, g, dt, eps=eps)
+        h = self._blocks(self._conv_in(images))
+        ca, cb = ops.group_norm_coeffs(h, *self.gn_out, self.cfg.groups, self.dt, eps=1e-6)
         return self._output(h, ca, cb)
 
     # ---- input gradient (d loss / d images through the frozen encoder: pixel-space optimisation against SD) ---------------------------
     # The decoder's scheme (VaeDecoderEngine) in the other direction.  forward_train() issues forward()'s launch sequence and keeps, per
     # ResnetBlock2D, x, the GN1 coefficients and partials, h and the GN2 ones; for the mid attention its input, GN, q|k|v and P; the last h
     # with its GN.  Down-samplers and convolutions are linear: nothing is kept.  backward() walks the tape once: quant_conv^T, conv_out^T,
-    # GroupNorm + SiLU backward, the mid block, the plan in reverse (_vae_res_back; a down-sampler's adjoint is ONE phased pmi_igemm launch,
+    # GroupNorm + SiLU backward, the mid block, the plan in reverse (_res_back; a down-sampler's adjoint is ONE phased pmi_igemm launch,
     # _down_back), conv_in^T with fp32 output, NCHW.
     @torch.no_grad()
     def forward_train(self, images: torch.Tensor):
         """As forward(), keeping what backward() needs: ((mean, logvar), tape).  For head dims above 160 (SD-v1: 512) the values equal
         forward()'s bit for bit; a 64-channel mid attention runs forward()'s d64 kernel there and the batched GEMMs here (rounding-level)."""
-        cfg, dt, w = self.cfg, self.dt, self.w
-        h = self._conv_in(images)
-        g, eps = cfg.groups, 1e-6
         rec: List[tuple] = []
-        for kind, k in self.plan:
-            if kind == "res":
-                h = self._vae_resnet_train(k, h, rec, g, eps)
-            else:
-                rec.append(("down", k))
-                h = self._down(h, w[k])
-        h = self._vae_resnet_train("encoder.mid_block.resnets.0", h, rec, g, eps)
-        h = self._vae_attention_train("encoder.mid_block.attentions.0", h, rec, g)
-        h = self._vae_resnet_train("encoder.mid_block.resnets.1", h, rec, g, eps)
-        ca, cb, parts = ops.group_norm_coeffs_train(h, *self.gn_out, g, dt, eps=eps)
-        mean, logvar = self._output(h, ca, cb)
-        tape = {"rec": rec, "last": (h, (ca, cb, parts)), "in_shape": tuple(images.shape), "out_shape": tuple(mean.shape)}
+        h = self._blocks(self._conv_in(images), rec)
+        gn = ops.group_norm_coeffs_train(h, *self.gn_out, self.cfg.groups, self.dt, eps=1e-6)
+        mean, logvar = self._output(h, gn[0], gn[1])
+        tape = {"rec": rec, "last": (h, gn), "in_shape": tuple(images.shape), "out_shape": tuple(mean.shape)}
         return (mean, logvar), tape
 
     def _quant_back(self, sd, both: bool) -> PackedLinear:
@@ -1043,7 +1001,7 @@ class VaeEncoderEngine(_Blocks):
         g, _ = ops.group_norm_backward(h, d_act, *gn, self.gn_out[0], g_, dt, act=ACT_SILU, eps=eps)
         for rec in reversed(tape["rec"]):
             if rec[0] == "res":
-                g = self._vae_res_back(rec, g, sd, g_, eps)
+                g, _ = self._res_back(rec, g, sd, g_, eps)
             elif rec[0] == "attn":
                 g = self._vae_attn_back(rec, g, sd, g_)
             else:

@@ -235,22 +235,31 @@ class VDiffEngine:
         a = ops.attention(qkv.view(n, hh * ww, 3 * c), ops.logical_c(x, dt) // self.spec.get("head_dim", 64), 1, dt)
         return ops.igemm(a.view(n * hh * ww, c), w[p + ".out"], residual=x.view(n * hh * ww, c)).view(n, hh, ww, c)
 
-    def _run(self, prog, prefix, x, mod):
+    def _run(self, prog, prefix, x, mod, tape=None):
+        """The block program `prog` on x.  With a tape (training mode) the blocks run in their _train forms -- other kernels: the norm unfused,
+        relu(conv2) kept apart from the skip add -- and every step appends its record for _back; a Skip's records are one nested list."""
         x1 = None
         for i, l in enumerate(prog):
             p = f"{prefix}.{i}"
             if isinstance(l, Res):
-                x, x1 = self._res(l, p, x, x1, mod), None
+                x, x1 = (self._res(l, p, x, x1, mod) if tape is None else self._res_train(l, p, x, x1, tape, mod)), None
             elif isinstance(l, Attn):
-                x = self._attn(l, p, x)
+                x = self._attn(l, p, x) if tape is None else self._attn_train(l, p, x, tape)
             elif isinstance(l, Down):
                 x = ops.avgpool2(x, self.dt)
+                if tape is not None:
+                    tape.append(("down",))
             elif isinstance(l, Up):
                 x = ops.upsample_nearest2(x) if self.spec.get("up_mode") == "nearest" else ops.upsample_bilinear2(x, self.dt)
+                if tape is not None:
+                    tape.append(("up",))
             elif isinstance(l, Skip):
+                inner_tape = None if tape is None else []
+                inner = self._run(l.main, p + ".main", x, mod, inner_tape)
+                if tape is not None:
+                    tape.append(("skip", inner_tape))
                 # torch.cat([main(x), x], dim=1): main first, then the skip path (yfcc_2.py:31-38);
                 # wikiart concatenates the other way round (wikiart_256.py:86-87)
-                inner = self._run(l.main, p + ".main", x, mod)
                 x, x1 = (x, inner) if self.spec.get("skip_first") else (inner, x)
         assert x1 is None
         return x
@@ -380,35 +389,12 @@ class VDiffEngine:
         tape.append(("attn", l, p, x, saved))
         return y
 
-    def _run_train(self, prog, prefix, x, tape, mod=None):
-        x1 = None
-        for i, l in enumerate(prog):
-            p = f"{prefix}.{i}"
-            if isinstance(l, Res):
-                x, x1 = self._res_train(l, p, x, x1, tape, mod), None
-            elif isinstance(l, Attn):
-                x = self._attn_train(l, p, x, tape)
-            elif isinstance(l, Down):
-                x = ops.avgpool2(x, self.dt)
-                tape.append(("down",))
-            elif isinstance(l, Up):
-                x = ops.upsample_nearest2(x) if self.spec.get("up_mode") == "nearest" else ops.upsample_bilinear2(x, self.dt)
-                tape.append(("up",))
-            elif isinstance(l, Skip):
-                inner_tape = []
-                inner = self._run_train(l.main, p + ".main", x, inner_tape, mod)
-                tape.append(("skip", inner_tape))
-                # torch.cat([main(x), x], dim=1) (yfcc_2.py:31-38); wikiart concatenates the other way round (wikiart_256.py:86-87)
-                x, x1 = (x, inner) if self.spec.get("skip_first") else (inner, x)
-        assert x1 is None
-        return x
-
     @torch.no_grad()
     def forward_train(self, images: torch.Tensor, t: torch.Tensor, clip_embed: Optional[torch.Tensor] = None):
         """As forward(), keeping what backward() needs.  Returns (v NCHW fp32, tape)."""
         mod, x = self._embed_input(images, t, clip_embed)
         tape = []
-        y = self._run_train(self.spec["net"], "net", x, tape, mod)
+        y = self._run(self.spec["net"], "net", x, mod, tape)
         return self._output(y), tape
 
     def _mask(self, g, y):
