@@ -493,6 +493,34 @@ int pmi_rdb_conv3x3(const void* X, int ldx, int Cin, const void* Wp, const float
                     const void* R2, int ldr2, float alpha, float beta, float slope, int up, int images, int H, int W, int dtype,
                     pmi_stream_t s);
 
+/* ---- MonsterDiffusion: the k-diffusion UNet's FIR resamplers (fir.hip) and the EDM sampler algebra (sampling.hip) ----
+ * pmi_fir_down2 / pmi_fir_up2: Downsample2d / Upsample2d with the "linear" kernel (base/layers.py:208-241) on 16-bit NHWC (f16, bf16), C a
+ *   multiple of 8, pointers 16-byte aligned.  down: reflect-pad 1, depthwise 4x4 k k^T with k = [1, 3, 3, 1] / 8, stride 2, H and W even and
+ *   >= 2 -> [N, H/2, W/2, C].  up: reflect-pad 1, conv_transpose2d with (2k)(2k)^T, stride 2, padding 3, H and W >= 2 -> [N, 2H, 2W, C]; per
+ *   axis out[2y] = x[refl(y-1)]/4 + 3x[y]/4, out[2y+1] = 3x[y]/4 + x[refl(y+1)]/4 (refl: x[-1] = x[1], x[H] = x[H-2]).  fp32 sums, one
+ *   rounding at the store.  Any other shape or dtype: PMI_ERR_ARG, nothing written.
+ * pmi_edm_*: fp32 NCHW images in [0, 1] (x = 2 img - 1), sigma one value per sample (count N) or one for the batch (count 1); D = sigma_data.
+ *   stage_in:  x16 [N, H, W, Cpad] = c_in(sigma) x (channels 3.. zero), c_in = 1 / sqrt(D^2 + sigma^2); c_noise [sigma_n] = ln(sigma) / 4.
+ *   stage_out: denoised_xs = c_skip x + c_out F, c_skip = D^2 / (D^2 + sigma^2), c_out = sigma D / sqrt(D^2 + sigma^2); F = net_out fp32 NHWC,
+ *              ld values per pixel.
+ *   predict:   eps = (x - denoised_xs) / sigma; step = decode(denoised_xs + eps sigma_to); corr = decode(x_prev + (sigma - sigma_prev)
+ *              (eps + eps_prev) / 2); decode(x) = (x + 1) / 2.  Each output may be NULL (at least one is not); an output's inputs must be given.
+ *   inject_noise: decode(x + sqrt(sigma_rev^2 - sigma^2) noise s_noise).
+ *   lms:       decode(x + sum_{k < order} coeff_k eps_k), order 1..4, over `total` elements. */
+int pmi_fir_down2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_fir_up2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_edm_stage_in(const float* img, const float* sigma, int sigma_n, float sigma_data, void* x, float* c_noise, int N, int H, int W,
+                     int Cpad, int dtype, pmi_stream_t s);
+int pmi_edm_stage_out(const float* img, const float* net_out, int ld, const float* sigma, int sigma_n, float sigma_data, float* denoised_xs,
+                      int N, int H, int W, pmi_stream_t s);
+int pmi_edm_predict(const float* img, const float* denoised_xs, const float* sigma, int sigma_n, const float* sigma_to, int sigma_to_n,
+                    const float* prev_img, const float* prev_sigma, int prev_sigma_n, const float* prev_eps, float* eps_out,
+                    float* step_out, float* corr_out, int N, int64_t chw, pmi_stream_t s);
+int pmi_edm_inject_noise(const float* img, const float* sigma, int sigma_n, const float* sigma_rev, int sigma_rev_n, const float* noise,
+                         float s_noise, float* out, int N, int64_t chw, pmi_stream_t s);
+int pmi_edm_lms(const float* img, const float* eps0, const float* eps1, const float* eps2, const float* eps3, float coeff0, float coeff1,
+                float coeff2, float coeff3, int order, float* out, int64_t total, pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

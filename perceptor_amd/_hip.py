@@ -181,6 +181,14 @@ _PROTOS = {
     # Real-ESRGAN RRDBNet dense-block convolution (rrdb.hip)
     "pmi_rdb_conv3x3_eligible": ([_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I],),
     "pmi_rdb_conv3x3": ([_P, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _F, _F, _F, _I, _I, _I, _I, _I, _P],),
+    # MonsterDiffusion: FIR resamplers (fir.hip), EDM parameterisation and sampler updates (sampling.hip)
+    "pmi_fir_down2": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_fir_up2": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_edm_stage_in": ([_P, _P, _I, _F, _P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_edm_stage_out": ([_P, _P, _I, _P, _I, _F, _P, _I, _I, _I, _P],),
+    "pmi_edm_predict": ([_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _L, _P],),
+    "pmi_edm_inject_noise": ([_P, _P, _I, _P, _I, _P, _F, _P, _I, _L, _P],),
+    "pmi_edm_lms": ([_P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _P, _L, _P],),
 }
 
 

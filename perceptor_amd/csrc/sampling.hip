@@ -4,6 +4,8 @@
 //   pmi_sort_rows        ascending sort of every row (wasserstein_*)           predictions.py:184-198
 //   pmi_wasserstein      mean |sorted - icdf(linspace)|^p against the standard normal
 //   pmi_clamp_grad       backward of clamp_with_grad                           transforms/clamp_with_grad.py:8-23
+//   pmi_edm_*            Karras et al.'s EDM parameterisation and the sampler updates of MonsterDiffusion (sigma is the time variable)
+//                                                                              monster_diffusion.py:85-125,187-196, prediction.py:61-121
 // All of it is HBM/L2-bound integer and elementwise work: coalesced 4-byte streams, LDS histograms, no MFMA.
 #include "../../include/perceptor_hip.h"
 #include "common.h"
@@ -267,6 +269,98 @@ __global__ __launch_bounds__(256) void clamp_grad_kernel(const float* __restrict
   out[i] = gi * ((gi * (v - c) >= 0.f) ? 1.f : 0.f);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------ EDM
+// Images are fp32 NCHW in [0, 1], x = 2 * img - 1 (standardize.encode), decode(x) = (x + 1) / 2.  sigma is one value per sample or ONE value
+// for the whole batch (sn = 1: index 0 is read for every sample), as PredictionBatch.sigmas broadcasts a 0-dim ts.  With D = sigma_data:
+//   c_in = 1 / sqrt(D^2 + sigma^2), c_skip = D^2 / (D^2 + sigma^2), c_out = sigma D / sqrt(D^2 + sigma^2), c_noise = ln(sigma) / 4.
+// Every formula is evaluated in fp32 in the order written here, with IEEE division and square root.
+__device__ __forceinline__ float edm_sigma(const float* sigma, int sn, int n) { return sigma[sn == 1 ? 0 : n]; }
+
+// stage-in: c_in * x as 16-bit NHWC, the 3 channels padded to Cpad with zeros (the only rounding to 16 bit), and c_noise per sigma
+template <typename T>
+__global__ __launch_bounds__(256) void edm_stage_in_kernel(const float* __restrict__ img, const float* __restrict__ sigma, int sn, float sd,
+                                                           u16* __restrict__ x, float* __restrict__ c_noise, int N, int HW, int Cpad) {
+  const int C8 = Cpad >> 3;
+  const int64_t total = (int64_t)N * HW * C8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c8 = (int)(i % C8);
+    const int64_t pix = i / C8;
+    const int n = (int)(pix / HW);
+    const int64_t p = pix - (int64_t)n * HW;
+    const float sg = edm_sigma(sigma, sn, n);
+    const float c_in = 1.f / sqrtf(sd * sd + sg * sg);
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = c8 * 8 + e;
+      f[e] = c < 3 ? c_in * (img[((int64_t)n * 3 + c) * HW + p] * 2.f - 1.f) : 0.f;
+    }
+    *(uint4*)(x + pix * Cpad + c8 * 8) = pack8<T>(f);
+    if (i < sn) c_noise[i] = 0.25f * logf(sigma[i]);
+  }
+}
+
+// stage-out: denoised_xs = c_skip * x + c_out * F from the network's fp32 NHWC output F (ld values per pixel), NCHW
+__global__ __launch_bounds__(256) void edm_stage_out_kernel(const float* __restrict__ img, const float* __restrict__ F, int ld,
+                                                            const float* __restrict__ sigma, int sn, float sd, float* __restrict__ den,
+                                                            int N, int HW) {
+  const int64_t total = (int64_t)N * 3 * HW;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t p = i % HW;
+    const int64_t nc = i / HW;
+    const int c = (int)(nc % 3), n = (int)(nc / 3);
+    const float sg = edm_sigma(sigma, sn, n);
+    const float s2 = sd * sd + sg * sg;
+    const float c_skip = sd * sd / s2, c_out = sg * sd / sqrtf(s2);
+    den[i] = c_skip * (img[i] * 2.f - 1.f) + c_out * F[((int64_t)n * HW + p) * ld + c];
+  }
+}
+
+// PredictionBatch.eps / .step / .correction from one read of (diffused image, denoised_xs); each output is optional:
+//   eps  = (x - denoised) / sigma
+//   step = decode(denoised + eps * sigma_to)
+//   corr = decode(x_prev + (sigma - sigma_prev) * (eps + eps_prev) / 2)
+__global__ __launch_bounds__(256) void edm_predict_kernel(const float* __restrict__ img, const float* __restrict__ den, const float* __restrict__ sigma,
+                                                          int sn, const float* __restrict__ sigma_to, int stn, const float* __restrict__ prev_img,
+                                                          const float* __restrict__ prev_sigma, int spn, const float* __restrict__ prev_eps,
+                                                          float* __restrict__ eps_out, float* __restrict__ step_out, float* __restrict__ corr_out,
+                                                          int N, int64_t chw) {
+  const int64_t total = (int64_t)N * chw;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int n = (int)(i / chw);
+    const float sg = edm_sigma(sigma, sn, n);
+    const float d = den[i];
+    const float e = ((img[i] * 2.f - 1.f) - d) / sg;
+    if (eps_out) eps_out[i] = e;
+    if (step_out) step_out[i] = ((d + e * edm_sigma(sigma_to, stn, n)) + 1.f) * 0.5f;
+    if (corr_out) corr_out[i] = (((prev_img[i] * 2.f - 1.f) + (sg - edm_sigma(prev_sigma, spn, n)) * (e + prev_eps[i]) * 0.5f) + 1.f) * 0.5f;
+  }
+}
+
+// inject_noise: decode(x + sqrt(sigma_rev^2 - sigma^2) * noise * S_noise)
+__global__ __launch_bounds__(256) void edm_inject_noise_kernel(const float* __restrict__ img, const float* __restrict__ sigma, int sn,
+                                                               const float* __restrict__ sigma_rev, int srn, const float* __restrict__ noise,
+                                                               float s_noise, float* __restrict__ out, int N, int64_t chw) {
+  const int64_t total = (int64_t)N * chw;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int n = (int)(i / chw);
+    const float sg = edm_sigma(sigma, sn, n), sr = edm_sigma(sigma_rev, srn, n);
+    out[i] = (((img[i] * 2.f - 1.f) + sqrtf(sr * sr - sg * sg) * noise[i] * s_noise) + 1.f) * 0.5f;
+  }
+}
+
+// linear multistep update: decode(x + sum_k coeff_k * eps_k), k < K <= 4, summed in order from k = 0 (the newest eps)
+struct edm_lms_terms { const float* eps[4]; float coeff[4]; };
+__global__ __launch_bounds__(256) void edm_lms_kernel(const float* __restrict__ img, edm_lms_terms t, int K, float* __restrict__ out, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < K) acc += t.coeff[k] * t.eps[k][i];
+    out[i] = (((img[i] * 2.f - 1.f) + acc) + 1.f) * 0.5f;
+  }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)s)
@@ -339,6 +433,66 @@ extern "C" int pmi_clamp_grad(const float* x, const float* grad, const float* lo
   if (!x || !grad || !lo || !hi || !out || N <= 0 || chw <= 0) return PMI_ERR_ARG;
   const int64_t total = (int64_t)N * chw;
   hipLaunchKernelGGL(clamp_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST, x, grad, lo, hi, out, chw, total);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+static inline int edm_grid(int64_t work) {
+  const int64_t b = (work + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
+}
+static inline bool edm_count_ok(int count, int N) { return count == 1 || count == N; }
+
+extern "C" int pmi_edm_stage_in(const float* img, const float* sigma, int sigma_n, float sigma_data, void* x, float* c_noise, int N, int H, int W,
+                                int Cpad, int dtype, pmi_stream_t s) {
+  if (!img || !sigma || !x || !c_noise || N <= 0 || H <= 0 || W <= 0 || Cpad < 8 || (Cpad & 7) || !edm_count_ok(sigma_n, N) || !(sigma_data > 0.f) ||
+      (dtype != PMI_DT_F16 && dtype != PMI_DT_BF16) || ((uintptr_t)x & 15))
+    return PMI_ERR_ARG;
+  dim3 grid(edm_grid((int64_t)N * H * W * (Cpad / 8))), block(256);
+  if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(edm_stage_in_kernel<BF16>, grid, block, 0, ST, img, sigma, sigma_n, sigma_data, (u16*)x, c_noise, N, H * W, Cpad);
+  else hipLaunchKernelGGL(edm_stage_in_kernel<F16>, grid, block, 0, ST, img, sigma, sigma_n, sigma_data, (u16*)x, c_noise, N, H * W, Cpad);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_edm_stage_out(const float* img, const float* net_out, int ld, const float* sigma, int sigma_n, float sigma_data, float* denoised_xs,
+                                 int N, int H, int W, pmi_stream_t s) {
+  if (!img || !net_out || !sigma || !denoised_xs || N <= 0 || H <= 0 || W <= 0 || ld < 3 || !edm_count_ok(sigma_n, N) || !(sigma_data > 0.f)) return PMI_ERR_ARG;
+  hipLaunchKernelGGL(edm_stage_out_kernel, dim3(edm_grid((int64_t)N * 3 * H * W)), dim3(256), 0, ST, img, net_out, ld, sigma, sigma_n, sigma_data, denoised_xs, N, H * W);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_edm_predict(const float* img, const float* denoised_xs, const float* sigma, int sigma_n, const float* sigma_to, int sigma_to_n,
+                               const float* prev_img, const float* prev_sigma, int prev_sigma_n, const float* prev_eps, float* eps_out,
+                               float* step_out, float* corr_out, int N, int64_t chw, pmi_stream_t s) {
+  if (!img || !denoised_xs || !sigma || N <= 0 || chw <= 0 || !edm_count_ok(sigma_n, N) || (!eps_out && !step_out && !corr_out)) return PMI_ERR_ARG;
+  if (step_out && (!sigma_to || !edm_count_ok(sigma_to_n, N))) return PMI_ERR_ARG;
+  if (corr_out && (!prev_img || !prev_sigma || !prev_eps || !edm_count_ok(prev_sigma_n, N))) return PMI_ERR_ARG;
+  hipLaunchKernelGGL(edm_predict_kernel, dim3(edm_grid(N * chw)), dim3(256), 0, ST, img, denoised_xs, sigma, sigma_n, sigma_to, sigma_to_n, prev_img,
+                     prev_sigma, prev_sigma_n, prev_eps, eps_out, step_out, corr_out, N, chw);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_edm_inject_noise(const float* img, const float* sigma, int sigma_n, const float* sigma_rev, int sigma_rev_n, const float* noise,
+                                    float s_noise, float* out, int N, int64_t chw, pmi_stream_t s) {
+  if (!img || !sigma || !sigma_rev || !noise || !out || N <= 0 || chw <= 0 || !edm_count_ok(sigma_n, N) || !edm_count_ok(sigma_rev_n, N)) return PMI_ERR_ARG;
+  hipLaunchKernelGGL(edm_inject_noise_kernel, dim3(edm_grid(N * chw)), dim3(256), 0, ST, img, sigma, sigma_n, sigma_rev, sigma_rev_n, noise, s_noise, out, N, chw);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_edm_lms(const float* img, const float* eps0, const float* eps1, const float* eps2, const float* eps3, float coeff0, float coeff1,
+                           float coeff2, float coeff3, int order, float* out, int64_t total, pmi_stream_t s) {
+  const float* e[4] = {eps0, eps1, eps2, eps3};
+  if (!img || !out || total <= 0 || order < 1 || order > 4) return PMI_ERR_ARG;
+  for (int k = 0; k < order; ++k)
+    if (!e[k]) return PMI_ERR_ARG;
+  edm_lms_terms t;
+  const float c[4] = {coeff0, coeff1, coeff2, coeff3};
+  for (int k = 0; k < 4; ++k) { t.eps[k] = k < order ? e[k] : nullptr; t.coeff[k] = k < order ? c[k] : 0.f; }
+  hipLaunchKernelGGL(edm_lms_kernel, dim3(edm_grid(total)), dim3(256), 0, ST, img, t, order, out, total);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }

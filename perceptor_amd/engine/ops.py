@@ -839,6 +839,22 @@ def upsample_bilinear2(x: torch.Tensor, dt: int) -> torch.Tensor:
     return y
 
 
+def fir_down2(x: torch.Tensor, dt: int) -> torch.Tensor:
+    """k-diffusion's Downsample2d("linear", reflect): [N, H, W, C] -> [N, H/2, W/2, C] (csrc/fir.hip)."""
+    n, h, w, c = x.shape
+    y = _empty((n, h // 2, w // 2, c), x.dtype, x.device)
+    call("pmi_fir_down2", ptr(x), ptr(y), n, h, w, c, dt)
+    return y
+
+
+def fir_up2(x: torch.Tensor, dt: int) -> torch.Tensor:
+    """k-diffusion's Upsample2d("linear", reflect): [N, H, W, C] -> [N, 2H, 2W, C] (csrc/fir.hip)."""
+    n, h, w, c = x.shape
+    y = _empty((n, h * 2, w * 2, c), x.dtype, x.device)
+    call("pmi_fir_up2", ptr(x), ptr(y), n, h, w, c, dt)
+    return y
+
+
 def upsample_nearest2(x: torch.Tensor) -> torch.Tensor:
     n, h, w, c = x.shape
     y = _empty((n, h * 2, w * 2, c), x.dtype, x.device)

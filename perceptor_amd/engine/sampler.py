@@ -72,6 +72,58 @@ def guided_update(pred, grad, s_f, scale: float, clamp_value: float):
     return out
 
 
+# ----------------------------------------------------------------------------------- EDM (MonsterDiffusion: sigma is the time)
+def edm_sigma(v, n: int, device) -> torch.Tensor:
+    """A sigma argument as the pmi_edm_* kernels take it: fp32 [1] (one value for the batch) or [n] on the device."""
+    if not torch.is_tensor(v):
+        return torch.full((1,), float(v), dtype=torch.float32, device=device)
+    v = v.to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+    if v.numel() not in (1, n):
+        raise ValueError(f"sigma has {v.numel()} values for a batch of {n}")
+    return v
+
+
+def edm_predict(images, denoised_xs, sigma, *, eps=False, to_sigma=None, previous=None):
+    """PredictionBatch.eps / .step(to_sigma) / .correction(*previous) in one launch; previous = (images, sigma, eps).
+    Returns (eps, step, correction), None where not asked for."""
+    images, den = _prep(images), _prep(denoised_xs)
+    n, chw, dev = images.shape[0], images[0].numel(), images.device
+    sg = edm_sigma(sigma, n, dev)
+    st = edm_sigma(to_sigma, n, dev) if to_sigma is not None else None
+    pi = ps = pe = None
+    if previous is not None:
+        pi, ps, pe = _prep(previous[0]), edm_sigma(previous[1], n, dev), _prep(previous[2])
+    e = torch.empty_like(images) if eps else None
+    s = torch.empty_like(images) if st is not None else None
+    c = torch.empty_like(images) if previous is not None else None
+    call("pmi_edm_predict", ptr(images), ptr(den), ptr(sg), sg.numel(), ptr(st), st.numel() if st is not None else 0, ptr(pi), ptr(ps),
+         ps.numel() if ps is not None else 0, ptr(pe), ptr(e), ptr(s), ptr(c), n, chw)
+    return e, s, c
+
+
+def edm_inject_noise(images, sigma, reversed_sigma, noise, s_noise: float):
+    """decode(x + sqrt(reversed_sigma^2 - sigma^2) * noise * s_noise)"""
+    images, noise = _prep(images), _prep(noise)
+    n, chw, dev = images.shape[0], images[0].numel(), images.device
+    sg, sr = edm_sigma(sigma, n, dev), edm_sigma(reversed_sigma, n, dev)
+    out = torch.empty_like(images)
+    call("pmi_edm_inject_noise", ptr(images), ptr(sg), sg.numel(), ptr(sr), sr.numel(), ptr(noise), float(s_noise), ptr(out), n, chw)
+    return out
+
+
+def edm_lms(images, coeffs, epses):
+    """decode(x + sum_k coeffs[k] * epses[k]) for up to four stored eps (host coefficients)."""
+    images = _prep(images)
+    es = [_prep(e) for e in epses]
+    if not 1 <= len(es) <= 4 or len(coeffs) != len(es):
+        raise ValueError("linear multistep update: between one and four (coefficient, eps) pairs")
+    out = torch.empty_like(images)
+    ep = [ptr(e) for e in es] + [None] * (4 - len(es))
+    cf = [float(c) for c in coeffs] + [0.0] * (4 - len(es))
+    call("pmi_edm_lms", ptr(images), *ep, *cf, len(es), ptr(out), images.numel())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- device RNG
 class DeviceRng:
     """Counter-based normal noise for the stochastic Predictions variants (csrc/sampling.hip: Philox4x32-10 + Box-Muller).

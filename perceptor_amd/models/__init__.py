@@ -7,3 +7,4 @@ from .transformers_openai_clip import TransformersOpenAICLIP
 from .simulacra_aesthetic import SimulacraAesthetic
 from .vgg import VGG19
 from .super_resolution import SuperResolution
+from .monster_diffusion import MonsterDiffusion
