@@ -521,6 +521,30 @@ int pmi_edm_inject_noise(const float* img, const float* sigma, int sigma_n, cons
 int pmi_edm_lms(const float* img, const float* eps0, const float* eps1, const float* eps2, const float* eps3, float coeff0, float coeff1,
                 float coeff2, float coeff3, int order, float* out, int64_t total, pmi_stream_t s);
 
+/* ---- Real-ESRGAN U-Net discriminator: the image gradient's own kernels (disc.hip) ----
+ * Replaces: the autograd backward of Conv2d(Cin, Cout, 4, 2, 1, bias=False) -- torch.nn.grad.conv2d_input / F.conv_transpose2d(g, W,
+ *   stride=2, padding=1) -- fused with the skip-gradient addition and the LeakyReLU mask of the layer before it, and F.leaky_relu /
+ *   its backward and Tensor.mean of unet_discriminator_sn.py:34-63 and discriminator.py:28-29.
+ * pmi_convt4x4s2: G [images, h, w, ldg] 16-bit NHWC gradient (Cout channels used) -> D [images, 2h, 2w, ldd] (Cin channels written):
+ *   acc[2p+a, 2q+b, ci] = sum_{u,v in {0,1}} sum_co W[co, ci, ky(a,u), kx(b,v)] G[p+a-1+u, q+b-1+v, co], ky(0,u) = 3 - 2u, ky(1,u) = 2 - 2u
+ *   (kx alike), G zero outside the image; D = (acc + R) * (Y >= 0 ? 1 : slope) with R, Y optional 16-bit NHWC on D's grid with their own
+ *   pitches.  fp32 accumulation, one rounding at the store; out_f32 = 1: D is fp32 (ldd counts floats).  Wp: the weights packed per phase
+ *   in fragment order [Cin / 16][phase = 2a + b][Cout / 32][2u + v][q = 4][r = 16][j = 8] = W[32 chunk + 8 q + j][16 block + r][ky][kx]
+ *   (engine/disc.py: pack_convt_weights).  Cout % 32 == 0, 32 .. 512; Cin % 32 == 0; pitches % 8 == 0 and >= their channel count; every
+ *   pointer 16-byte aligned; any h, w >= 1.  Only the Cin channels of D's pixels are written.
+ * pmi_convt4x4s2_eligible: host only, 1 when pmi_convt4x4s2 takes the shape (ldr / ldy = 0: that operand absent), else 0; pmi_convt4x4s2
+ *   then (and for a misaligned or NULL pointer, out_f32 outside {0, 1} or a non-finite slope) returns PMI_ERR_ARG without a launch.
+ * pmi_lrelu_bwd: dz = (g + g2) * (y >= 0 ? 1 : slope) over n 16-bit values, g2 optional; pmi_lrelu_add: y = lrelu_slope(z) + r, r optional.
+ *   fp32 arithmetic, one rounding at the store; any n >= 1, pointers 16-byte aligned.
+ * pmi_mean_f32: out[0] = scale * sum_{i < n} x[i] in a fixed order (256 contiguous ranges summed by one workgroup each into partial[256],
+ *   then one tree over the partials): two runs are bit-equal. */
+int pmi_convt4x4s2_eligible(int Cout, int Cin, int ldg, int ldd, int ldr, int ldy, int images, int h, int w, int dtype);
+int pmi_convt4x4s2(const void* G, int ldg, int Cout, const void* Wp, int Cin, void* D, int ldd, const void* R, int ldr, const void* Y, int ldy,
+                   float slope, int out_f32, int images, int h, int w, int dtype, pmi_stream_t s);
+int pmi_lrelu_bwd(const void* g, const void* g2, const void* y, void* dz, int64_t n, float slope, int dtype, pmi_stream_t s);
+int pmi_lrelu_add(const void* z, const void* r, void* y, int64_t n, float slope, int dtype, pmi_stream_t s);
+int pmi_mean_f32(const float* x, float* partial, float* out, int64_t n, float scale, pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

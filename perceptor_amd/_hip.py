@@ -189,6 +189,12 @@ _PROTOS = {
     "pmi_edm_predict": ([_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _L, _P],),
     "pmi_edm_inject_noise": ([_P, _P, _I, _P, _I, _P, _F, _P, _I, _L, _P],),
     "pmi_edm_lms": ([_P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _P, _L, _P],),
+    # Real-ESRGAN U-Net discriminator gradient (disc.hip)
+    "pmi_convt4x4s2_eligible": ([_I, _I, _I, _I, _I, _I, _I, _I, _I, _I],),
+    "pmi_convt4x4s2": ([_P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _F, _I, _I, _I, _I, _I, _P],),
+    "pmi_lrelu_bwd": ([_P, _P, _P, _P, _L, _F, _I, _P],),
+    "pmi_lrelu_add": ([_P, _P, _P, _L, _F, _I, _P],),
+    "pmi_mean_f32": ([_P, _P, _P, _L, _F, _P],),
 }
 
 

@@ -4,7 +4,8 @@ super-resolved down-sampling,
 both resizes with ``resample=mode`` and the second only when the up-sampled shape differs from the images'.  As upstream the up-sampled
 images are a constant (computed without gradient): the gradient is 2 (images - upsampled) / count, which pmi_sqdiff_loss writes with
 the value.  ``forward`` is a scalar that works with ``.backward()``; ``loss_and_grad`` is the fused path without autograd.
-SuperResolutionDiscriminator is not provided.
+SuperResolutionDiscriminator, the other export of the reference's package, is losses/super_resolution_discriminator.py (imported from
+that module; `losses` itself does not re-export it).
 """
 from __future__ import annotations
 
