@@ -16,14 +16,15 @@ padding lives in the normalised space -- so pmi_rn_stage_input applies them whil
 Only the input gradient is needed (frozen weights): dX of a convolution is the forward convolution on transposed, flipped weights; the
 stride-2 stem convolution's dX is a stride-1 convolution of the zero-inserted gradient (engine/adm.py does the same); the post-ReLU
 outputs double as the ReLU masks of pmi_act_bwd.  Activations and gradients are 16-bit NHWC (bf16 by default; f16 scales the gradient by
-a power of two, as engine/vit.py does).
+a power of two: gscale = 65536 on the caller's side, as engine/vit.py does, times one chosen in backward() from the largest |d_emb| -- the
+gradient shrinks by three to four orders of magnitude on its way to the stem and a fixed scale leaves it among f16's subnormals).
 
 State-dict keys follow open_clip's ``visual.*``: conv{1,2,3}.weight, bn{1,2,3}.*, layer{1..4}.{i}.conv{1,2,3}.weight / .bn{1,2,3}.* /
 .downsample.0.weight / .downsample.1.*, attnpool.positional_embedding, attnpool.{q,k,v,c}_proj.{weight,bias}.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -43,6 +44,9 @@ RN_CONFIGS = {
     "RN50x64": (448, (3, 15, 36, 10), 128, 64, 1024),
 }
 BN_EPS = 1e-5
+# f16 backward: where the largest |d_emb| is put (ops.f16_grad_scale's (0.5, 1] times this).  What the fixed gscale = 65536 gives at a loss
+# gradient of ~1e-2: a factor 64 below f16's largest value, and the stem's gradients (~1e-4 of d_emb's) stay normal numbers.
+F16_DEMB_TOP = 1024.0
 
 
 def blocks(cfg):
@@ -158,8 +162,11 @@ class ResNetEngine:
 
     # ---- forward --------------------------------------------------------------------------------------
     @torch.no_grad()
-    def forward(self, images: torch.Tensor, save: bool = False):
-        """images NCHW fp32 in [0,1] (any size) -> un-normalised embeddings [N, out_dim] fp32."""
+    def forward(self, images: torch.Tensor, save: bool = False, record: Optional[dict] = None):
+        """images NCHW fp32 in [0,1] (any size) -> un-normalised embeddings [N, out_dim] fp32.
+        record (tests): a dict that receives references to tensors this pass makes anyway and `saved` does not keep (no launch, no copy):
+        resized (the image at the tower's resolution), x0 (the staged stem input), pooled (the stem's output), x_in (every block's input, in
+        forward order), tok, o."""
         if not images.is_cuda:
             raise RuntimeError("ResNetEngine runs on a HIP device only (no CPU fallback)")
         res, layers, width, heads, out = self.cfg
@@ -173,8 +180,12 @@ class ResNetEngine:
         s2 = ops.igemm(s1, self.stem[1].fwd, act=ACT_RELU)
         s3 = ops.igemm(s2, self.stem[2].fwd, act=ACT_RELU)
         x = ops.avgpool2(s3, dt)
+        if record is not None:
+            record.update(resized=resized, x0=x0, pooled=x, x_in=[])
         tape = []
         for blk in self.blocks:
+            if record is not None:
+                record["x_in"].append(x)
             h1 = ops.igemm(x, blk["c1"].fwd, act=ACT_RELU)
             h2 = ops.igemm(h1, blk["c2"].fwd, act=ACT_RELU)
             h2p = ops.avgpool2(h2, dt) if blk["stride"] > 1 else h2
@@ -198,14 +209,21 @@ class ResNetEngine:
         P = torch.empty((n * heads, t), dtype=torch.float32, device=dev)
         call("pmi_rn_attn_fwd", ptr(q), ptr(kv), ptr(o), ptr(P), n, t, c, heads, 64.0 ** -0.5, dt)
         emb = ops.igemm(o, self.cp, out_f32=True)
+        if record is not None:
+            record.update(tok=tok, o=o)
         if save:
             self.saved = dict(in_hw=tuple(images.shape[2:]), n=n, stem=(s1, s2, s3), tape=tape, feat_hw=(hh, ww), q=q, kv=kv, P=P)
         return emb[:, :out] if emb.shape[1] != out else emb
 
     # ---- input gradient -----------------------------------------------------------------------------------
     @torch.no_grad()
-    def backward(self, d_emb: torch.Tensor) -> torch.Tensor:
-        """d_emb: dL/d(embedding) * self.gscale, fp32 [N, out_dim]  ->  dL/d(images), fp32 NCHW."""
+    def backward(self, d_emb: torch.Tensor, record: Optional[dict] = None) -> torch.Tensor:
+        """d_emb: dL/d(embedding) * self.gscale, fp32 [N, out_dim]  ->  dL/d(images), fp32 NCHW.  (f16 multiplies d_emb by a further power of
+        two chosen from its largest value, ops.f16_grad_scale: one host read of n floats.)
+        record (tests): a dict that receives references to gradient tensors this pass makes anyway (no launch, no copy; all but dres are times
+        `scale`, the whole power of two, which it receives as well): d_o, dq, dkv, dtok, dq0, g (the gradient at every block boundary: at the
+        last block's output first, at the first block's input last), stem (the gradients at s3, s2 and s1, after their ReLU masks), dx (the
+        stem convolution's fp32 dX), dres (the gradient of the resized image)."""
         sv = self.saved
         if sv is None:
             raise RuntimeError("call forward(images, save=True) before backward()")
@@ -219,6 +237,15 @@ class ResNetEngine:
         t = hw + 1
         d16 = torch.empty((n, out), dtype=tdt, device=dev)
         d_emb = d_emb.contiguous()          # named: a temporary would be released before the launch is queued
+        scale = self.gscale
+        if dt == _hip.DT_F16:
+            # the gradient shrinks by three to four orders of magnitude from the embedding to the stem: whatever size the caller's loss
+            # gradient has, a further power of two (exact) puts its largest value into (F16_DEMB_TOP / 2, F16_DEMB_TOP]
+            amax = torch.empty((n,), dtype=torch.float32, device=dev)
+            call("pmi_quantile_abs", ptr(d_emb), ptr(amax), n, out, 1.0)
+            extra = ops.f16_grad_scale(amax.tolist()) * F16_DEMB_TOP
+            if extra != 1.0:
+                d_emb, scale = d_emb * extra, scale * extra
         call("pmi_cast_f32_to_16", ptr(d_emb), ptr(d16), n * out, ACT_NONE, dt)
         d_o = ops.igemm(d16, self.cp_t)                                          # [n, c]
         dq = torch.empty((n, c), dtype=tdt, device=dev)
@@ -228,6 +255,8 @@ class ResNetEngine:
         dq0 = ops.igemm(dq, self.q_t, out_f32=True)                              # [n, c]: the query path's share of row 0
         g = torch.empty((n, hh, ww, c), dtype=tdt, device=dev)
         call("pmi_rn_tokens_bwd", ptr(dtok), ptr(dq0), ptr(g), n, hw, c, dt)
+        if record is not None:
+            record.update(d_o=d_o, dq=dq, dkv=dkv, dtok=dtok, dq0=dq0, g=[g])
         for blk, (h1, h2, y) in zip(reversed(self.blocks), reversed(sv["tape"])):
             gy = self._relu_bwd(g, y)
             gh = ops.igemm(gy, blk["c3"].bwd)
@@ -242,15 +271,23 @@ class ResNetEngine:
             else:
                 gs = gy
             g = ops.igemm(gh, blk["c1"].bwd, residual=gs)                        # conv1's dX + the skip path's gradient in one epilogue
+            if record is not None:
+                record["g"].append(g)
         s1, s2, s3 = sv["stem"]
+        note = record.setdefault("stem", []).append if record is not None else (lambda t: None)
         g = self._relu_bwd(ops.avgpool2_bwd(g, self.dt), s3)
+        note(g)
         g = self._relu_bwd(ops.igemm(g, self.stem[2].bwd), s2)
+        note(g)
         g = self._relu_bwd(ops.igemm(g, self.stem[1].bwd), s1)
+        note(g)
         nb, h_, w_, cg = g.shape             # stride-2 convolution: dX = stride-1 convolution of the zero-inserted gradient, flipped weights
         z = torch.zeros((nb, 2 * h_, 2 * w_, cg), dtype=g.dtype, device=dev)
         z[:, ::2, ::2] = g
         dx = ops.igemm(z, self.stem[0].bwd, out_f32=True)                        # [n, res, res, 4]: channels 0..2 are the image's
         dres = torch.empty((n, 3, res, res), dtype=torch.float32, device=dev)
-        call("pmi_rn_stage_input_bwd", ptr(dx), dx.shape[-1], ptr(self.std), ptr(dres), n, res, res, 1.0 / self.gscale)
+        call("pmi_rn_stage_input_bwd", ptr(dx), dx.shape[-1], ptr(self.std), ptr(dres), n, res, res, 1.0 / scale)
+        if record is not None:
+            record.update(dx=dx, dres=dres, scale=scale)
         self.saved = None
         return _resize_backward(dres, sv["in_hw"])

@@ -1,7 +1,9 @@
 """GPU parity of the CLIP ResNet image towers (engine/resnet.py, csrc/resnet.hip) against float64 references.
 
 Kernel level: the attention-pool kernels against tests/_ref64.py's float64 attention with its elementwise worst-case rounding bounds, the
-input-staging and token kernels against float64 and against their adjoints.  Tower level: tests/_rn_ref64.py (unfolded BatchNorm, float64)
+input-staging and token kernels against float64 and against their adjoints; then their edge shapes (every length at which the
+attention kernels' loops change shape, T = 1 and RN_TMAX, the token and staging adjoints per element, more items than the elementwise kernels'
+capped grids hold), outputs inside guard bands, refusals with nothing written.  Tower level: tests/_rn_ref64.py (unfolded BatchNorm, float64)
 with the ViT bounds of tests/test_gpu_clip.py: embedding rel-L2 <= 1e-2 against the exact tower, image-gradient rel-L2 <= 2e-2 and cosine
 >= 0.9995 against the float64 tower pinned to the engine's ReLU masks (why: _tower_case).  RN50x64 (too slow for a float64 CPU pass in a
 test) is checked by properties: determinism, batch independence and bf16 / f16 agreement.
@@ -119,6 +121,241 @@ def test_tokens_vs_fp64_and_adjoint(n, hw, C, dtype):
     rhs = float((x * dx.double().cpu()).sum())
     bound = u * float((x.abs() * (y[:, 1:].abs() + (y[:, :1].abs() + dq0.double().abs()[:, None]) / hw)).sum()) * 1.01
     assert abs(lhs - rhs) <= bound, (lhs, rhs, bound)
+
+
+# ---- kernel level: edge shapes, guard bands, refusals ---------------------------------------------------------------------------------------
+GRID_ITEMS = 8192 * 256           # grid_for() caps the elementwise kernels' grids at 8192 workgroups of 256 threads: more items than this
+PAD = 256                         # and a thread takes a second step of its grid-stride loop.  PAD: guard bytes on each side of an output
+FILL = 0x7B                       # 0x7B7B = 6.1e4 in f16, 1.3e36 in bf16; 0x7B7B7B7B = 1.3e36 in fp32: nothing a kernel under test writes
+
+
+def _guarded(shape, td):
+    """an output tensor inside guard bands of FILL bytes, itself pre-filled with them: (tensor, whole buffer)"""
+    nbytes = torch.empty((), dtype=td).element_size()
+    for d in shape:
+        nbytes *= d
+    buf = torch.full((PAD + nbytes + PAD,), FILL, dtype=torch.uint8, device="cuda")
+    return buf[PAD:PAD + nbytes].view(td).view(shape), buf
+
+
+def _bands_intact(buf):
+    return bool((buf[:PAD] == FILL).all()) and bool((buf[-PAD:] == FILL).all())
+
+
+def _untouched(buf):
+    return bool((buf == FILL).all())
+
+
+def _refused(name, *args):
+    with pytest.raises(RuntimeError, match="bad argument"):
+        _call(name, *args)
+
+
+ATTN_EDGE_T = [1, 2, 5, 31, 32, 33, 255, 256, 257, 513, 1024]       # idle row groups (< 32), one row, the second step of the t += 256 loops, RN_TMAX
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+@pytest.mark.parametrize("T", ATTN_EDGE_T)
+def test_attnpool_attention_edge_lengths(T, dtype):
+    """pmi_rn_attn_fwd / _bwd at every length where their loops change shape, heads 1 and 8, n 1 and 3, four score regimes (mass spread,
+    near one-hot, on the first key, on the last key), outputs inside guard bands; at T = 1 the softmax is 1 and dK is 0 exactly"""
+    td = R64.TD[dtype]
+    for heads, n, regime in [(h, n, r) for h in (1, 8) for n in (1, 3) for r in ("flat", "peaked", "first", "last")]:
+        C, B = 64 * heads, n * heads
+        tag = f"T={T} heads={heads} n={n} {regime} {dtype}"
+        q, k, v = R64.attn_inputs(B, 1, 64, regime, dtype, seed=T + 7 * heads + n, Tk=T, scale=0.125)
+        g = torch.Generator().manual_seed(T + heads + n)
+        dout = R64.rnd(torch.randn(B, 1, 64, generator=g, dtype=torch.float64), dtype)
+        r = R64.attn_ref(q, k, v, dout, scale=0.125)
+        if regime in ("first", "last") and T > 1:
+            top = r["P"].argmax(dim=-1)
+            assert bool((top == (0 if regime == "first" else T - 1)).all()), tag
+        tok = lambda z: z.view(n, heads, T, 64).permute(0, 2, 1, 3).reshape(n * T, C)
+        qd = q.view(n, C).to(td).cuda()
+        kv = torch.cat([tok(k), tok(v)], dim=1).to(td).cuda().contiguous()
+        o, o_buf = _guarded((n, C), td)
+        P, p_buf = _guarded((B, T), torch.float32)
+        _call("pmi_rn_attn_fwd", _p(qd), _p(kv), _p(o), _p(P), n, T, C, heads, 0.125, DT[dtype])
+        torch.cuda.synchronize()
+        assert _bands_intact(o_buf) and _bands_intact(p_buf), tag
+        R64.check(f"rn attn edge O {tag}", o.view(B, 1, 64), r["O"], R64.attn_tol(r, "O", dtype))
+        R64.check(f"rn attn edge P {tag}", P.view(B, 1, T), r["P"], 1e-5 * float(r["P"].max()))
+        do = dout.view(n, C).to(td).cuda()
+        dq, dq_buf = _guarded((n, C), td)
+        dkv, dkv_buf = _guarded((n * T, 2 * C), td)
+        _call("pmi_rn_attn_bwd", _p(qd), _p(kv), _p(P), _p(do), _p(dq), _p(dkv), n, T, C, heads, 0.125, DT[dtype])
+        torch.cuda.synchronize()
+        assert _bands_intact(dq_buf) and _bands_intact(dkv_buf), tag
+        heads_of = lambda z: z.reshape(n, T, heads, 64).permute(0, 2, 1, 3).reshape(B, T, 64)
+        dk, dv = heads_of(dkv[:, :C]), heads_of(dkv[:, C:])
+        R64.check(f"rn attn edge dQ {tag}", dq.view(B, 1, 64), r["dQ"], R64.attn_tol(r, "dQ", dtype))
+        R64.check(f"rn attn edge dK {tag}", dk, r["dK"], R64.attn_tol(r, "dK", dtype))
+        R64.check(f"rn attn edge dV {tag}", dv, r["dV"], R64.attn_tol(r, "dV", dtype))
+        if T == 1:
+            assert bool((P == 1.0).all()) and bool((dk == 0).all()), tag
+            assert torch.equal(o.view(B, 64), v.view(B, 64).to(td).cuda())          # the one value row, as stored
+
+
+def test_attnpool_attention_refuses_without_writing():
+    """T = 0, T = RN_TMAX + 1, C != 64 heads and an unknown dtype are refused before any launch: no output byte changes"""
+    n, heads, T = 2, 2, 1025
+    C = 64 * heads
+    q = torch.zeros((n, C), dtype=torch.bfloat16, device="cuda")
+    kv = torch.zeros((n * T, 2 * C), dtype=torch.bfloat16, device="cuda")
+    do = torch.zeros((n, C), dtype=torch.bfloat16, device="cuda")
+    Pin = torch.zeros((n * heads, T), dtype=torch.float32, device="cuda")
+    o, o_buf = _guarded((n, C), torch.bfloat16)
+    P, p_buf = _guarded((n * heads, T), torch.float32)
+    dq, dq_buf = _guarded((n, C), torch.bfloat16)
+    dkv, dkv_buf = _guarded((n * T, 2 * C), torch.bfloat16)
+    for t_, c_, h_, dt_ in [(0, C, heads, 1), (1025, C, heads, 1), (50, C + 64, heads, 1), (50, C - 8, heads, 1), (50, C, 0, 1), (50, C, heads, 2), (50, C, heads, 7)]:
+        _refused("pmi_rn_attn_fwd", _p(q), _p(kv), _p(o), _p(P), n, t_, c_, h_, 0.125, dt_)
+        _refused("pmi_rn_attn_bwd", _p(q), _p(kv), _p(Pin), _p(do), _p(dq), _p(dkv), n, t_, c_, h_, 0.125, dt_)
+    _call("pmi_rn_attn_fwd", _p(q), _p(kv), _p(o), _p(P), n, 1024, C, heads, 0.125, 1)       # RN_TMAX itself is taken
+    torch.cuda.synchronize()
+    assert _bands_intact(o_buf) and not _untouched(o_buf)
+    assert _untouched(dq_buf) and _untouched(dkv_buf)
+    o2, o2_buf = _guarded((n, C), torch.bfloat16)
+    P2, p2_buf = _guarded((n * heads, T), torch.float32)
+    _refused("pmi_rn_attn_fwd", _p(q), _p(kv), _p(o2), _p(P2), n, 1025, C, heads, 0.125, 1)
+    torch.cuda.synchronize()
+    assert _untouched(o2_buf) and _untouched(p2_buf)
+
+
+def _tokens_bwd_case(n, hw, C, dtype, seed, with_dq0):
+    """pmi_rn_tokens_bwd per element: dx = dtok[1 + p] + (dtok[0] + dq0) / HW within 1.01 u |terms| (the one 16-bit rounding) + 2^-21 |terms|
+    (the fp32 steps: 1 / HW, two sums, one product), the output inside guard bands"""
+    td, u = R64.TD[dtype], R64.U[dtype]
+    g = torch.Generator().manual_seed(seed)
+    y = R64.rnd(torch.randn(n, hw + 1, C, generator=g, dtype=torch.float64), dtype)
+    dq0 = torch.randn(n, C, generator=g, dtype=torch.float64).float()
+    y_d, dq0_d = y.to(td).cuda().view(n * (hw + 1), C), dq0.cuda()
+    dx, buf = _guarded((n, hw, C), td)
+    _call("pmi_rn_tokens_bwd", _p(y_d), _p(dq0_d) if with_dq0 else None, _p(dx), n, hw, C, DT[dtype])
+    torch.cuda.synchronize()
+    assert _bands_intact(buf)
+    row0 = y[:, :1] + (dq0.double()[:, None] if with_dq0 else 0.0)
+    want = y[:, 1:] + row0 / hw
+    terms = y[:, 1:].abs() + (y[:, :1].abs() + (dq0.double().abs()[:, None] if with_dq0 else 0.0)) / hw
+    err = (dx.double().cpu() - want).abs()
+    tol = (1.01 * u + 2.0 ** -21) * terms
+    tag = f"rn tokens_bwd n={n} hw={hw} C={C} dq0={'given' if with_dq0 else 'NULL'} {dtype}"
+    R64.parity(tag, float((err / tol).max()), 1.0)
+    assert bool((err <= tol).all()), tag
+    return err, tol
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+@pytest.mark.parametrize("C", [8, 512, 2560])
+@pytest.mark.parametrize("hw", [1, 4, 9, 49])
+def test_tokens_bwd_per_element(hw, C, dtype):
+    for with_dq0 in (True, False):
+        _tokens_bwd_case(3, hw, C, dtype, hw * 31 + C, with_dq0)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+@pytest.mark.parametrize("ldc", [4, 8])
+@pytest.mark.parametrize("mul", [1.0, 2.0 ** -16])
+def test_stage_input_bwd_per_element(mul, ldc, dtype):
+    """pmi_rn_stage_input_bwd per element against float64: dimg = dx / std * mul, two fp32 roundings; the channels past the third of dx (the
+    convolution's pad channels) hold NaN and are never read.  (No 16-bit type in this kernel: dtype picks the seed only.)"""
+    from perceptor_amd.engine.vit import CLIP_STD
+    n, h, w = (2, 33, 39) if dtype == "bf16" else (3, 50, 56)
+    g = torch.Generator().manual_seed(ldc + n)
+    dx = torch.randn(n, h, w, ldc, generator=g, dtype=torch.float64).float()
+    dx[..., 3:] = float("nan")
+    std = torch.tensor(CLIP_STD)
+    dx_d, std_d = dx.cuda(), std.cuda()
+    out, buf = _guarded((n, 3, h, w), torch.float32)
+    _call("pmi_rn_stage_input_bwd", _p(dx_d), ldc, _p(std_d), _p(out), n, h, w, mul)
+    torch.cuda.synchronize()
+    assert _bands_intact(buf)
+    want = dx[..., :3].double().permute(0, 3, 1, 2) / std.double().view(1, 3, 1, 1) * mul
+    err = (out.double().cpu() - want).abs()
+    tol = 2.02 * 2.0 ** -24 * want.abs()
+    R64.parity(f"rn stage_input_bwd n={n} {h}x{w} ldc={ldc} mul={mul:g}", float((err / tol.clamp_min(1e-300)).max()), 1.0)
+    assert bool((err <= tol).all())
+    _refused("pmi_rn_stage_input_bwd", _p(dx_d), 2, _p(std_d), _p(out), n, h, w, mul)
+
+
+def _first_last(err, tol, tag):
+    e, t = err.flatten(), tol.flatten()
+    assert float(e[0]) <= float(t[0]) and float(e[-1]) <= float(t[-1]), (tag, float(e[0]), float(t[0]), float(e[-1]), float(t[-1]))
+
+
+def test_stage_input_grid_stride():
+    """n * h * w = 8192 * 256 + 1 items: the smallest count at which a thread of pmi_rn_stage_input takes a second grid-stride step"""
+    from perceptor_amd.engine.vit import CLIP_MEAN, CLIP_STD
+    from perceptor_amd.utils.synth import seeded_noise
+    n, h, w = 1, 1, GRID_ITEMS + 1
+    u = R64.U["bf16"]
+    img = seeded_noise((n, 3, h, w), 5) * 0.25 + 0.5
+    mean, std = torch.tensor(CLIP_MEAN).cuda(), torch.tensor(CLIP_STD).cuda()
+    img_d = img.cuda()
+    x, buf = _guarded((n, h, w, 8), torch.bfloat16)
+    _call("pmi_rn_stage_input", _p(img_d), _p(mean), _p(std), _p(x), n, h, w, DT["bf16"])
+    torch.cuda.synchronize()
+    assert _bands_intact(buf)
+    want = RN.normalize(img).permute(0, 2, 3, 1)
+    err = (x[..., :3].double().cpu() - want).abs()
+    # one 16-bit rounding and the fp32 subtraction and division; absolute where x is near its channel's mean: the fp32 constants' own
+    # rounding, 2^-25 mean / std <= 2^-24 (mean / std < 1.9)
+    tol = (1.01 * u + 2.0 ** -21) * want.abs() + 2.0 ** -24 * (1.0 + 2.0 ** -7)
+    R64.parity(f"rn stage_input grid stride {n}x{h}x{w}", float((err / tol).max()), 1.0)
+    assert bool((err <= tol).all())
+    _first_last(err, tol, "stage_input")
+    assert float(x[..., 3:].abs().max()) == 0.0
+
+
+def test_stage_input_bwd_grid_stride():
+    """n * 3 * h * w = 8192 * 256 + 1 items"""
+    from perceptor_amd.engine.vit import CLIP_STD
+    from perceptor_amd.utils.synth import seeded_noise
+    n, h, w = 1, 1, (GRID_ITEMS + 1) // 3
+    assert n * 3 * h * w == GRID_ITEMS + 1
+    dx = seeded_noise((n, h, w, 4), 6)
+    std = torch.tensor(CLIP_STD)
+    dx_d, std_d = dx.cuda(), std.cuda()
+    out, buf = _guarded((n, 3, h, w), torch.float32)
+    _call("pmi_rn_stage_input_bwd", _p(dx_d), 4, _p(std_d), _p(out), n, h, w, 0.5)
+    torch.cuda.synchronize()
+    assert _bands_intact(buf)
+    want = dx[..., :3].double().permute(0, 3, 1, 2) / std.double().view(1, 3, 1, 1) * 0.5
+    err = (out.double().cpu() - want).abs()
+    tol = 2.02 * 2.0 ** -24 * want.abs()
+    R64.parity(f"rn stage_input_bwd grid stride {n}x{h}x{w}", float((err / tol.clamp_min(1e-300)).max()), 1.0)
+    assert bool((err <= tol).all())
+    _first_last(err, tol, "stage_input_bwd")
+
+
+def test_tokens_grid_stride():
+    """n * (hw + 1) * C / 8 = 6554 * 320 > 8192 * 256 items at the product's widest-but-one C = 2560 (6553 * 320 is below)"""
+    n, hw, C, dtype = 1, 6553, 2560, "bf16"
+    assert n * hw * (C // 8) <= GRID_ITEMS < n * (hw + 1) * (C // 8)
+    td, u = R64.TD[dtype], R64.U[dtype]
+    g = torch.Generator().manual_seed(hw)
+    x = R64.rnd(torch.randn(n, hw, C, generator=g, dtype=torch.float64), dtype)
+    pos = torch.randn(hw + 1, C, generator=g, dtype=torch.float64).float()
+    x_d, pos_d = x.to(td).cuda(), pos.cuda()
+    tok, buf = _guarded((n * (hw + 1), C), td)
+    _call("pmi_rn_tokens", _p(x_d), _p(pos_d), _p(tok), n, hw, C, DT[dtype])
+    torch.cuda.synchronize()
+    assert _bands_intact(buf)
+    want = torch.cat([x.mean(dim=1, keepdim=True), x], dim=1) + pos.double()[None]
+    scale = torch.cat([x.abs().mean(dim=1, keepdim=True), x.abs()], dim=1) + pos.double().abs()[None]
+    err = (tok.view(n, hw + 1, C).double().cpu() - want).abs()
+    tol = (1.01 * u + (hw + 2) * 2.0 ** -24) * scale          # one 16-bit rounding + the worst case of an fp32 sum of hw terms in order
+    R64.parity(f"rn tokens grid stride n={n} hw={hw} C={C}", float((err / tol).max()), 1.0)
+    assert bool((err <= tol).all())
+    _first_last(err, tol, "tokens")
+
+
+def test_tokens_bwd_grid_stride():
+    """n * hw * C / 8 = 6554 * 320 > 8192 * 256 items"""
+    n, hw, C = 1, 6554, 2560
+    assert n * (hw - 1) * (C // 8) <= GRID_ITEMS < n * hw * (C // 8)
+    err, tol = _tokens_bwd_case(n, hw, C, "bf16", 11, True)
+    _first_last(err, tol, "tokens_bwd")
 
 
 # ---- tower level ------------------------------------------------------------------------------------------------------------------------
