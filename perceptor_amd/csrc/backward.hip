@@ -15,6 +15,7 @@
 //                               shaped like the forward's stats / finalize / apply
 #include "../../include/perceptor_hip.h"
 #include "common.h"
+#include "launch_util.h"
 
 namespace {
 
@@ -239,10 +240,8 @@ __global__ __launch_bounds__(GT) void gn1_bwd_apply_kernel(const u16* __restrict
   }
 }
 
-inline unsigned grid_for(int64_t items) {
-  const int64_t b = (items + 255) / 256;
-  return (unsigned)(b < 1 ? 1 : (b > 65535 * 16 ? 65535 * 16 : b));
-}
+// this file's grid-stride kernels take up to 65535 * 16 workgroups
+inline int grid_for(int64_t items) { return grid_256(items, 65535 * 16); }
 
 
 // ---- GroupNorm(G) (+FiLM) + activation backward (ADM UNet) --------------------------------------------------------------------------

@@ -16,6 +16,12 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 FILE_FLAGS = {"conv_wd.hip": ["-fno-slp-vectorize"], "conv_up_wd.hip": ["-fno-slp-vectorize"]}
 
 
+def headers() -> list:
+    """Every header a source here may include: each is a dependency of every object."""
+    own = sorted(os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h"))
+    return own + [os.path.normpath(os.path.join(HERE, "..", "..", "include", "perceptor_hip.h"))]
+
+
 def _stale(out: str, deps) -> bool:
     if not os.path.exists(out):
         return True
@@ -29,7 +35,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", extra_f
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     lib = LIB if not variant else LIB.replace(".so", f"_{variant}.so")
     bdir = "build" if not variant else f"build_{variant}"
-    hdrs = [os.path.join(HERE, "common.h"), os.path.join(HERE, "..", "..", "include", "perceptor_hip.h")]
+    hdrs = headers()
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
     objs = []
 

@@ -3,14 +3,10 @@
 // forward and adjoint share one kernel), patchify / unpatchify (Normalize fused), token assembly
 // and the spherical-distance loss with its gradient through F.normalize.
 #include "common.h"
+#include "launch_util.h"
 #include "../../include/perceptor_hip.h"
 
 namespace {
-
-inline int grid_for(int64_t work) {
-  int64_t b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
 
 // ---- LayerNorm forward: one wave per row, fp32 in, 16-bit and/or fp32 out -------------------------
 template <typename T>
@@ -498,13 +494,13 @@ extern "C" int pmi_softmax_causal_fwd(const float* S, void* P, int rows, int T, 
 extern "C" int pmi_embed_tokens(const int64_t* ids, const float* tok, const float* pos, float* x, int N, int T, int D, int vocab, pmi_stream_t s) {
   if (!ids || !tok || !x || N <= 0 || T <= 0 || D <= 0 || vocab <= 0) return PMI_ERR_ARG;
   const int64_t total = (int64_t)N * T * D;
-  hipLaunchKernelGGL(embed_tokens_kernel, dim3(grid_for(total)), dim3(256), 0, ST, ids, tok, pos, x, total, T, D, vocab);
+  hipLaunchKernelGGL(embed_tokens_kernel, dim3(grid_256(total)), dim3(256), 0, ST, ids, tok, pos, x, total, T, D, vocab);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_gather_rows(const float* src, const int64_t* idx, float* dst, int R, int D, int ld, int64_t src_rows, pmi_stream_t s) {
   if (!src || !idx || !dst || R <= 0 || D <= 0 || ld < D || src_rows <= 0) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for((int64_t)R * D)), dim3(256), 0, ST, src, idx, dst, R, D, ld, src_rows);
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_256((int64_t)R * D)), dim3(256), 0, ST, src, idx, dst, R, D, ld, src_rows);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
@@ -526,7 +522,7 @@ extern "C" int pmi_transpose_16(const void* in, void* out, int R, int Cc, int ld
 }
 extern "C" int pmi_act_bwd(const void* dh, const void* hpre, void* out, int64_t n, int act, int dtype, pmi_stream_t s) {
   if (!dh || !hpre || !out || n <= 0 || (n & 7)) return PMI_ERR_ARG;
-  dim3 grid(grid_for(n / 8)), block(256);
+  dim3 grid(grid_256(n / 8)), block(256);
   BY_DTYPE(act_bwd_kernel, (const u16*)dh, (const u16*)hpre, (u16*)out, n / 8, act);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
@@ -535,7 +531,7 @@ extern "C" int pmi_resize_apply(const float* in, float* out, const int* idx, con
                                 int out_sz, int taps, int r0, int r1, pmi_stream_t s) {
   (void)r0; (void)r1;
   if (!in || !out || !idx || !w || outer <= 0 || in_sz <= 0 || inner <= 0 || out_sz <= 0 || taps <= 0) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(resize_apply_kernel, dim3(grid_for((int64_t)outer * out_sz * inner)), dim3(256), 0, ST, in, out, idx, w,
+  hipLaunchKernelGGL(resize_apply_kernel, dim3(grid_256((int64_t)outer * out_sz * inner)), dim3(256), 0, ST, in, out, idx, w,
                      outer, in_sz, inner, out_sz, taps);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
@@ -544,7 +540,7 @@ extern "C" int pmi_patchify(const float* img, const float* mean, const float* st
                             int r0, int dtype, pmi_stream_t s) {
   (void)r0;
   if (!img || !mean || !stdv || !col || N <= 0 || R <= 0 || P <= 0 || R % P || Kp < 3 * P * P || (Kp & 7)) return PMI_ERR_ARG;
-  dim3 grid(grid_for((int64_t)N * (R / P) * (R / P) * Kp)), block(256);
+  dim3 grid(grid_256((int64_t)N * (R / P) * (R / P) * Kp)), block(256);
   BY_DTYPE(patchify_kernel, img, mean, stdv, (u16*)col, N, R, P, Kp);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
@@ -552,14 +548,14 @@ extern "C" int pmi_patchify(const float* img, const float* mean, const float* st
 extern "C" int pmi_unpatchify(const float* dcol, const float* stdv, float* dimg, int N, int R, int P, int Kp, float mul, pmi_stream_t s) {
   // dcol is fp32: no Kp % 8 rule as in pmi_patchify, but every row must hold the 3 P^2 columns the kernel reads
   if (!dcol || !stdv || !dimg || N <= 0 || R <= 0 || P <= 0 || R % P || Kp < (int64_t)3 * P * P) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(unpatchify_kernel, dim3(grid_for((int64_t)N * 3 * R * R)), dim3(256), 0, ST, dcol, stdv, dimg, N, R, P, Kp, mul);
+  hipLaunchKernelGGL(unpatchify_kernel, dim3(grid_256((int64_t)N * 3 * R * R)), dim3(256), 0, ST, dcol, stdv, dimg, N, R, P, Kp, mul);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_vit_assemble(const float* emb, const float* cls, const float* pos, float* x, int N, int T, int D, int r0, pmi_stream_t s) {
   (void)r0;
   if (!emb || !cls || !pos || !x || N <= 0 || T <= 1 || D <= 0) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(vit_assemble_kernel, dim3(grid_for((int64_t)N * T * D)), dim3(256), 0, ST, emb, cls, pos, x, N, T, D);
+  hipLaunchKernelGGL(vit_assemble_kernel, dim3(grid_256((int64_t)N * T * D)), dim3(256), 0, ST, emb, cls, pos, x, N, T, D);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
@@ -573,7 +569,7 @@ extern "C" int pmi_spherical_loss(const float* emb, const float* tgt, const floa
 }
 extern "C" int pmi_act_fwd(const void* in, void* out, int64_t n, int act, int dtype, pmi_stream_t s) {
   if (!in || !out || n <= 0 || (n & 7)) return PMI_ERR_ARG;
-  dim3 grid(grid_for(n / 8)), block(256);
+  dim3 grid(grid_256(n / 8)), block(256);
   BY_DTYPE(act_fwd_kernel, (const u16*)in, (u16*)out, n / 8, act);
   PMI_CHECK_LAUNCH();
   return PMI_OK;

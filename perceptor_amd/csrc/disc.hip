@@ -22,6 +22,7 @@
 // fp32 logit map in a fixed two-stage order (256 contiguous ranges, then one tree), so two runs are bit-equal.
 #include "../../include/perceptor_hip.h"
 #include "common.h"
+#include "launch_util.h"
 
 namespace {
 
@@ -206,13 +207,6 @@ __global__ __launch_bounds__(256) void mean_stage2_kernel(const float* __restric
   if (threadIdx.x == 0) out[0] = s * scale;
 }
 
-inline bool finite_f(float v) { return v == v && v - v == 0.f; }
-
-inline int ew_blocks(int64_t n) {
-  const int64_t b = ((n >> 3) + 255) / 256;
-  return (int)(b < 1 ? 1 : b > 8192 ? 8192 : b);
-}
-
 }  // namespace
 
 extern "C" int pmi_convt4x4s2_eligible(int Cout, int Cin, int ldg, int ldd, int ldr, int ldy, int images, int h, int w, int dtype) {
@@ -255,9 +249,9 @@ extern "C" int pmi_lrelu_bwd(const void* g, const void* g2, const void* y, void*
   if (dtype != PMI_DT_F16 && dtype != PMI_DT_BF16) return PMI_ERR_ARG;
   if (((uintptr_t)g | (uintptr_t)g2 | (uintptr_t)y | (uintptr_t)dz) & 15) return PMI_ERR_ARG;
   if (dtype == PMI_DT_F16)
-    hipLaunchKernelGGL(lrelu_bwd_kernel<F16>, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)s, (const u16*)g, (const u16*)g2, (const u16*)y, (u16*)dz, n, slope);
+    hipLaunchKernelGGL(lrelu_bwd_kernel<F16>, dim3(grid_256(n >> 3)), dim3(256), 0, (hipStream_t)s, (const u16*)g, (const u16*)g2, (const u16*)y, (u16*)dz, n, slope);
   else
-    hipLaunchKernelGGL(lrelu_bwd_kernel<BF16>, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)s, (const u16*)g, (const u16*)g2, (const u16*)y, (u16*)dz, n, slope);
+    hipLaunchKernelGGL(lrelu_bwd_kernel<BF16>, dim3(grid_256(n >> 3)), dim3(256), 0, (hipStream_t)s, (const u16*)g, (const u16*)g2, (const u16*)y, (u16*)dz, n, slope);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
@@ -267,9 +261,9 @@ extern "C" int pmi_lrelu_add(const void* z, const void* r, void* y, int64_t n, f
   if (dtype != PMI_DT_F16 && dtype != PMI_DT_BF16) return PMI_ERR_ARG;
   if (((uintptr_t)z | (uintptr_t)r | (uintptr_t)y) & 15) return PMI_ERR_ARG;
   if (dtype == PMI_DT_F16)
-    hipLaunchKernelGGL(lrelu_add_kernel<F16>, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)s, (const u16*)z, (const u16*)r, (u16*)y, n, slope);
+    hipLaunchKernelGGL(lrelu_add_kernel<F16>, dim3(grid_256(n >> 3)), dim3(256), 0, (hipStream_t)s, (const u16*)z, (const u16*)r, (u16*)y, n, slope);
   else
-    hipLaunchKernelGGL(lrelu_add_kernel<BF16>, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)s, (const u16*)z, (const u16*)r, (u16*)y, n, slope);
+    hipLaunchKernelGGL(lrelu_add_kernel<BF16>, dim3(grid_256(n >> 3)), dim3(256), 0, (hipStream_t)s, (const u16*)z, (const u16*)r, (u16*)y, n, slope);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }

@@ -1,14 +1,10 @@
 // Layout conversion, pooling / upsampling, timestep features and the fused sampler updates.
 // All HBM-bound streaming kernels: grid-stride, 16-byte accesses where the layout allows.
 #include "common.h"
+#include "launch_util.h"
 #include "../../include/perceptor_hip.h"
 
 namespace {
-
-inline int grid_for(int64_t work) {
-  int64_t b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
 
 // NCHW fp32 image in [0,1] -> NHWC 16-bit x = 2*img-1, channels [3,3+nplanes) constant planes, rest zero.
 template <typename T>
@@ -335,33 +331,33 @@ __global__ __launch_bounds__(256) void clamp_kernel(const float* __restrict__ a,
 
 extern "C" int pmi_prep_input(const float* img, const float* planes, int nplanes, void* x, int N, int H, int W, int Cpad, int dtype, pmi_stream_t s) {
   if (!img || !x || N <= 0 || H <= 0 || W <= 0 || (Cpad & 7) || Cpad < 3 + nplanes || (nplanes > 0 && !planes)) return PMI_ERR_ARG;
-  dim3 grid(grid_for((int64_t)N * H * W * (Cpad / 8))), block(256);
+  dim3 grid(grid_256((int64_t)N * H * W * (Cpad / 8))), block(256);
   BY_DTYPE(prep_input_kernel, img, planes, nplanes, (u16*)x, N, H * W, Cpad);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_finish_output(const float* y, int ld, float* out, int N, int H, int W, int cout, pmi_stream_t s) {
   if (!y || !out || N <= 0 || cout <= 0 || cout > ld) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(finish_output_kernel, dim3(grid_for((int64_t)N * cout * H * W)), dim3(256), 0, ST, y, ld, out, N, H * W, cout);
+  hipLaunchKernelGGL(finish_output_kernel, dim3(grid_256((int64_t)N * cout * H * W)), dim3(256), 0, ST, y, ld, out, N, H * W, cout);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_nchw_to_nhwc(const float* in, void* x, int N, int C, int H, int W, int Cpad, float mul, float add, int dtype, pmi_stream_t s) {
   if (!in || !x || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (Cpad & 7) || Cpad < C) return PMI_ERR_ARG;
-  dim3 grid(grid_for((int64_t)N * H * W * (Cpad / 8))), block(256);
+  dim3 grid(grid_256((int64_t)N * H * W * (Cpad / 8))), block(256);
   BY_DTYPE(nchw_to_nhwc_kernel, in, (u16*)x, N, C, H * W, Cpad, mul, add);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_nhwc_to_nchw(const float* y, int ld, float* out, int N, int H, int W, int cout, float mul, float add, pmi_stream_t s) {
   if (!y || !out || N <= 0 || cout <= 0 || cout > ld) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_for((int64_t)N * cout * H * W)), dim3(256), 0, ST, y, ld, out, N, H * W, cout, mul, add);
+  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_256((int64_t)N * cout * H * W)), dim3(256), 0, ST, y, ld, out, N, H * W, cout, mul, add);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_geglu(const void* h, void* out, int64_t M, int F, int interleaved, int dtype, pmi_stream_t s) {
   if (!h || !out || M <= 0 || F <= 0 || (F & 7) || (interleaved && (F & 15)) || dtype == PMI_DT_F16X2) return PMI_ERR_ARG;
-  dim3 grid(grid_for(M * (F / 8))), block(256);
+  dim3 grid(grid_256(M * (F / 8))), block(256);
   if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(geglu_kernel<BF16>, grid, block, 0, ST, (const u16*)h, (u16*)out, M, F, interleaved);
   else hipLaunchKernelGGL(geglu_kernel<F16>, grid, block, 0, ST, (const u16*)h, (u16*)out, M, F, interleaved);
   PMI_CHECK_LAUNCH();
@@ -369,7 +365,7 @@ extern "C" int pmi_geglu(const void* h, void* out, int64_t M, int F, int interle
 }
 extern "C" int pmi_geglu_bwd(const void* h, const void* dg, void* dh, int64_t M, int F, int interleaved, int dtype, pmi_stream_t s) {
   if (!h || !dg || !dh || M <= 0 || F <= 0 || (F & 7) || (interleaved && (F & 15)) || dtype == PMI_DT_F16X2) return PMI_ERR_ARG;
-  dim3 grid(grid_for(M * (F / 8))), block(256);
+  dim3 grid(grid_256(M * (F / 8))), block(256);
   if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(geglu_bwd_kernel<BF16>, grid, block, 0, ST, (const u16*)h, (const u16*)dg, (u16*)dh, M, F, interleaved);
   else hipLaunchKernelGGL(geglu_bwd_kernel<F16>, grid, block, 0, ST, (const u16*)h, (const u16*)dg, (u16*)dh, M, F, interleaved);
   PMI_CHECK_LAUNCH();
@@ -377,21 +373,21 @@ extern "C" int pmi_geglu_bwd(const void* h, const void* dg, void* dh, int64_t M,
 }
 extern "C" int pmi_avgpool2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
   if (!x || !y || N <= 0 || (H & 1) || (W & 1) || (C & 7)) return PMI_ERR_ARG;
-  dim3 grid(grid_for((int64_t)N * (H / 2) * (W / 2) * (C / 8))), block(256);
+  dim3 grid(grid_256((int64_t)N * (H / 2) * (W / 2) * (C / 8))), block(256);
   BY_DTYPE(avgpool2_kernel, (const u16*)x, (u16*)y, N, H, W, C);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_upsample_bilinear2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
   if (!x || !y || N <= 0 || H <= 0 || W <= 0 || (C & 7)) return PMI_ERR_ARG;
-  dim3 grid(grid_for((int64_t)N * H * W * 4 * (C / 8))), block(256);
+  dim3 grid(grid_256((int64_t)N * H * W * 4 * (C / 8))), block(256);
   BY_DTYPE(upsample_bilinear2_kernel, (const u16*)x, (u16*)y, N, H, W, C);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_upsample_nearest2(const void* x, void* y, int N, int H, int W, int C, pmi_stream_t s) {
   if (!x || !y || N <= 0 || H <= 0 || W <= 0 || (C & 7)) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(upsample_nearest2_kernel, dim3(grid_for((int64_t)N * H * W * 4 * (C / 8))), dim3(256), 0, ST, (const u16*)x, (u16*)y, N, H, W, C);
+  hipLaunchKernelGGL(upsample_nearest2_kernel, dim3(grid_256((int64_t)N * H * W * 4 * (C / 8))), dim3(256), 0, ST, (const u16*)x, (u16*)y, N, H, W, C);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
@@ -404,19 +400,19 @@ extern "C" int pmi_timestep_embedding(const float* t, void* out, int N, int dim,
 }
 extern "C" int pmi_split_convert(const void* in, void* out, int64_t rows, int C, int to_split, pmi_stream_t s) {
   if (!in || !out || rows <= 0 || C <= 0 || (C & 7) || (C > 32 && (C & 31))) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(split_convert_kernel, dim3(grid_for(rows * (C / 8))), dim3(256), 0, ST, (const u16*)in, (u16*)out, rows, C, to_split);
+  hipLaunchKernelGGL(split_convert_kernel, dim3(grid_256(rows * (C / 8))), dim3(256), 0, ST, (const u16*)in, (u16*)out, rows, C, to_split);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_split_from_f32(const float* in, int ld_in, void* out, int64_t rows, int C, pmi_stream_t s) {
   if (!in || !out || rows <= 0 || C <= 0 || (C & 7) || (C > 32 && (C & 31)) || (ld_in & 3)) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(split_from_f32_kernel, dim3(grid_for(rows * (C / 8))), dim3(256), 0, ST, in, ld_in, (u16*)out, rows, C);
+  hipLaunchKernelGGL(split_from_f32_kernel, dim3(grid_256(rows * (C / 8))), dim3(256), 0, ST, in, ld_in, (u16*)out, rows, C);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_split_to_f32(const void* in, float* out, int64_t rows, int C, pmi_stream_t s) {
   if (!in || !out || rows <= 0 || C <= 0 || (C & 7) || (C > 32 && (C & 31))) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(split_to_f32_kernel, dim3(grid_for(rows * (C / 8))), dim3(256), 0, ST, (const u16*)in, out, rows, C);
+  hipLaunchKernelGGL(split_to_f32_kernel, dim3(grid_256(rows * (C / 8))), dim3(256), 0, ST, (const u16*)in, out, rows, C);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
@@ -428,7 +424,7 @@ extern "C" int pmi_fourier_features(const float* t, const float* w, float* out, 
 }
 extern "C" int pmi_cast_f32_to_16(const float* in, void* out, int64_t n, int act, int dtype, pmi_stream_t s) {
   if (!in || !out || n <= 0) return PMI_ERR_ARG;
-  dim3 grid(grid_for(n)), block(256);
+  dim3 grid(grid_256(n)), block(256);
   BY_DTYPE(cast_kernel, in, (u16*)out, n, act);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
@@ -436,34 +432,34 @@ extern "C" int pmi_cast_f32_to_16(const float* in, void* out, int64_t n, int act
 extern "C" int pmi_ddim_eps_step(const float* img, const float* eps, const float* a_from, const float* s_from, const float* a_to,
                                  const float* s_to, float* next_img, float* denoised_img, int N, int64_t chw, pmi_stream_t s) {
   if (!img || !eps || !a_from || !s_from || N <= 0 || chw <= 0 || (next_img && (!a_to || !s_to))) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(ddim_eps_kernel, dim3(grid_for(N * chw)), dim3(256), 0, ST, img, eps, a_from, s_from, a_to, s_to, next_img, denoised_img, N, chw);
+  hipLaunchKernelGGL(ddim_eps_kernel, dim3(grid_256(N * chw)), dim3(256), 0, ST, img, eps, a_from, s_from, a_to, s_to, next_img, denoised_img, N, chw);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_ddim_v_step(const float* img, const float* v, const float* a_from, const float* s_from, const float* a_to,
                                const float* s_to, float* next_img, float* denoised_img, int N, int64_t chw, pmi_stream_t s) {
   if (!img || !v || !a_from || !s_from || N <= 0 || chw <= 0 || (next_img && (!a_to || !s_to))) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(ddim_v_kernel, dim3(grid_for(N * chw)), dim3(256), 0, ST, img, v, a_from, s_from, a_to, s_to, next_img, denoised_img, N, chw);
+  hipLaunchKernelGGL(ddim_v_kernel, dim3(grid_256(N * chw)), dim3(256), 0, ST, img, v, a_from, s_from, a_to, s_to, next_img, denoised_img, N, chw);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_guided_update(const float* pred, const float* grad, const float* s_from, float scale, float clamp_value,
                                  float* out, int N, int64_t chw, pmi_stream_t s) {
   if (!pred || !grad || !s_from || !out || N <= 0 || chw <= 0 || !(clamp_value > 0.f)) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(guided_kernel, dim3(grid_for(N * chw)), dim3(256), 0, ST, pred, grad, s_from, scale, clamp_value, out, N, chw);
+  hipLaunchKernelGGL(guided_kernel, dim3(grid_256(N * chw)), dim3(256), 0, ST, pred, grad, s_from, scale, clamp_value, out, N, chw);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_lincomb2(const float* a, const float* b, const float* ca, const float* cb, const float* cc, float* out, int N,
                             int64_t chw, pmi_stream_t s) {
   if (!a || !ca || !out || N <= 0 || chw <= 0 || (b && !cb)) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(lincomb2_kernel, dim3(grid_for(N * chw)), dim3(256), 0, ST, a, b, ca, cb, cc, out, N, chw);
+  hipLaunchKernelGGL(lincomb2_kernel, dim3(grid_256(N * chw)), dim3(256), 0, ST, a, b, ca, cb, cc, out, N, chw);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 extern "C" int pmi_clamp(const float* a, const float* lo, const float* hi, float* out, int N, int64_t chw, pmi_stream_t s) {
   if (!a || !lo || !hi || !out || N <= 0 || chw <= 0) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(clamp_kernel, dim3(grid_for(N * chw)), dim3(256), 0, ST, a, lo, hi, out, N, chw);
+  hipLaunchKernelGGL(clamp_kernel, dim3(grid_256(N * chw)), dim3(256), 0, ST, a, lo, hi, out, N, chw);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }

@@ -6,14 +6,10 @@
 // The reflection is index arithmetic (no padded copy).  HBM-bound streaming kernels: one thread per output pixel and 8 channels, 16-byte
 // loads and stores, every tap weight (1, 3, 9 over 64 resp. 16) exact in fp32, fp32 sums, one rounding at the store.
 #include "common.h"
+#include "launch_util.h"
 #include "../../include/perceptor_hip.h"
 
 namespace {
-
-inline int grid_for(int64_t work) {
-  int64_t b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
 
 // index -1 .. n of an axis of n >= 2 samples under reflect padding by one
 __device__ __forceinline__ int refl(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
@@ -84,7 +80,7 @@ __global__ __launch_bounds__(256) void fir_up2_kernel(const u16* __restrict__ x,
 extern "C" int pmi_fir_down2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
   if (!x || !y || N <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1) || C <= 0 || (C & 7) || (dtype != PMI_DT_F16 && dtype != PMI_DT_BF16)) return PMI_ERR_ARG;
   if ((((uintptr_t)x | (uintptr_t)y) & 15)) return PMI_ERR_ARG;
-  dim3 grid(grid_for((int64_t)N * (H / 2) * (W / 2) * (C / 8))), block(256);
+  dim3 grid(grid_256((int64_t)N * (H / 2) * (W / 2) * (C / 8))), block(256);
   if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(fir_down2_kernel<BF16>, grid, block, 0, ST, (const u16*)x, (u16*)y, N, H, W, C);
   else hipLaunchKernelGGL(fir_down2_kernel<F16>, grid, block, 0, ST, (const u16*)x, (u16*)y, N, H, W, C);
   PMI_CHECK_LAUNCH();
@@ -94,7 +90,7 @@ extern "C" int pmi_fir_down2(const void* x, void* y, int N, int H, int W, int C,
 extern "C" int pmi_fir_up2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
   if (!x || !y || N <= 0 || H < 2 || W < 2 || C <= 0 || (C & 7) || (dtype != PMI_DT_F16 && dtype != PMI_DT_BF16)) return PMI_ERR_ARG;
   if ((((uintptr_t)x | (uintptr_t)y) & 15)) return PMI_ERR_ARG;
-  dim3 grid(grid_for((int64_t)N * H * W * 4 * (C / 8))), block(256);
+  dim3 grid(grid_256((int64_t)N * H * W * 4 * (C / 8))), block(256);
   if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(fir_up2_kernel<BF16>, grid, block, 0, ST, (const u16*)x, (u16*)y, N, H, W, C);
   else hipLaunchKernelGGL(fir_up2_kernel<F16>, grid, block, 0, ST, (const u16*)x, (u16*)y, N, H, W, C);
   PMI_CHECK_LAUNCH();

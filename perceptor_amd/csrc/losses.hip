@@ -12,20 +12,12 @@
 // products and takes the mean of their squares over N * K values -- it never sums the K products into an expectation.  That is kept.
 #include "../../include/perceptor_hip.h"
 #include "common.h"
+#include "launch_util.h"
 
 namespace {
 
 constexpr int LB = 1024;     // first-level slots (workgroups) of the image-sized reductions
 constexpr int HEAD_KMAX = 16, HEAD_DMAX = 4096;
-
-// sum over a 256-thread workgroup, the same value in every thread; `red` = 4 floats of LDS
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // ------------------------------------------------------------------------------------------------------------------ head loss
 // One workgroup per sample.  e = emb / max(|emb|, 1e-12); l[k] = sq * W[k].e + b[k] (sq = sqrt(D) in mode 0, else 1);
@@ -202,12 +194,6 @@ __global__ __launch_bounds__(256) void sqdiff_kernel(const float* __restrict__ a
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline unsigned slots_for(int64_t units) {
-  const int64_t nb = (units + 255) / 256;
-  return (unsigned)(nb < 1 ? 1 : (nb > LB ? LB : nb));
-}
-
 }  // namespace
 
 #define ST ((hipStream_t)s)
@@ -243,7 +229,7 @@ extern "C" int pmi_smoothness(const float* x, float* loss, float* grad, float* p
   const float gh = (float)(2.0 * gscale * inv_h), gw = (float)(2.0 * gscale * inv_w);
   const bool vec = W % 4 == 0 && aligned16(x) && aligned16(grad);
   const int64_t units = vec ? total / 4 : total;
-  const unsigned nblk = slots_for(units);
+  const unsigned nblk = grid_256(units, LB);
   if (vec) hipLaunchKernelGGL(smoothness_kernel<4>, dim3(nblk), dim3(256), 0, ST, x, grad, partial, units, H, W, gh, gw);
   else hipLaunchKernelGGL(smoothness_kernel<1>, dim3(nblk), dim3(256), 0, ST, x, grad, partial, units, H, W, gh, gw);
   PMI_CHECK_LAUNCH();
@@ -258,7 +244,7 @@ extern "C" int pmi_sqdiff_loss(const float* a, const float* b, float* loss, floa
   if (!a || !b || !loss || !g || !partial || count <= 0 || count >= ((int64_t)1 << 40) || n_total_count < count) return PMI_ERR_ARG;
   const double inv = 1.0 / (double)n_total_count;
   const int vec = aligned16(a) && aligned16(b) && aligned16(g);
-  const unsigned nblk = slots_for((count + 3) >> 2);
+  const unsigned nblk = grid_256((count + 3) >> 2, LB);
   hipLaunchKernelGGL(sqdiff_kernel, dim3(nblk), dim3(256), 0, ST, a, b, g, partial, count, vec, (float)(2.0 * inv));
   PMI_CHECK_LAUNCH();
   hipLaunchKernelGGL(slots_final_kernel, dim3(1), dim3(LB), 0, ST, partial, (int)nblk, 1, loss, (float)inv, 0.f);

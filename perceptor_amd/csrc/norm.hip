@@ -1,6 +1,7 @@
 // GroupNorm (statistics, coefficient finalisation, fused apply) and LayerNorm (fwd / input-grad)
 // for gfx950.  All HBM-bound: 16-byte vector accesses, fp32 statistics, wave64 reductions.
 #include "common.h"
+#include "launch_util.h"
 #include "../../include/perceptor_hip.h"
 
 namespace {
@@ -206,11 +207,6 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const u16* __restrict__ x
   }
 }
 
-inline int grid_for(int64_t work) {
-  int64_t b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 2048 * 4 ? 2048 * 4 : b));
-}
-
 }  // namespace
 
 extern "C" int pmi_gn_stats(const void* x, const void* x1, int C0, float* ws, int N, int HW, int C, int G, int nchunk, int dtype, pmi_stream_t s) {
@@ -258,7 +254,7 @@ extern "C" int pmi_gn_apply(const void* x, const void* x1, int C0, const float* 
   if (!x || !y || !coef_a || !coef_b || N <= 0 || H <= 0 || W <= 0 || (C & 7)) return PMI_ERR_ARG;
   if (pool && ((H & 1) || (W & 1))) return PMI_ERR_ARG;
   const int64_t work = (int64_t)N * (pool ? H / 2 : H) * (pool ? W / 2 : W) * (C / 8);
-  dim3 grid(grid_for(work)), block(256);
+  dim3 grid(grid_256(work)), block(256);
   hipStream_t st = (hipStream_t)s;
 #define GO(TT, PP) hipLaunchKernelGGL((gn_apply_kernel<TT, PP>), grid, block, 0, st, (const u16*)x, (const u16*)x1, C0, coef_a, coef_b, (const u16*)res, (u16*)y, N, H, W, C, act, (u16*)nullptr)
   if (dtype == PMI_DT_BF16) { if (pool) GO(BF16, true); else GO(BF16, false); }
@@ -274,7 +270,7 @@ extern "C" int pmi_gn_apply_pool_skip(const void* x, const float* coef_a, const 
                                       int act, int dtype, pmi_stream_t s) {
   if (!x || !y || !y_raw || !coef_a || !coef_b || N <= 0 || H <= 0 || W <= 0 || (C & 7) || (H & 1) || (W & 1)) return PMI_ERR_ARG;
   const int64_t work = (int64_t)N * (H / 2) * (W / 2) * (C / 8);
-  dim3 grid(grid_for(work)), block(256);
+  dim3 grid(grid_256(work)), block(256);
   hipStream_t st = (hipStream_t)s;
 #define GO(TT) hipLaunchKernelGGL((gn_apply_kernel<TT, true, true>), grid, block, 0, st, (const u16*)x, (const u16*)nullptr, C, coef_a, coef_b, (const u16*)nullptr, (u16*)y, N, H, W, C, act, (u16*)y_raw)
   if (dtype == PMI_DT_BF16) GO(BF16);

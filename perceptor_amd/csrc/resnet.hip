@@ -9,16 +9,12 @@
 // keeps the T <= RN_TMAX scores / probabilities in LDS and writes no T x T or transposed buffer.
 #include "../../include/perceptor_hip.h"
 #include "common.h"
+#include "launch_util.h"
 
 #define RN_TMAX 1024
 #define RN_HEAD 64
 
 namespace {
-
-inline int grid_for(int64_t work) {
-  int64_t b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
 
 // ---- stem input staging ------------------------------------------------------------------------------------------------------
 template <typename T>
@@ -249,28 +245,28 @@ __global__ __launch_bounds__(256) void rn_attn_bwd_kernel(const u16* __restrict_
 extern "C" int pmi_rn_stage_input(const float* img, const float* mean, const float* stdv, void* out, int N, int H, int W, int dtype,
                                   pmi_stream_t s) {
   if (!img || !mean || !stdv || !out || N <= 0 || H <= 0 || W <= 0 || !RN_DTYPE_OK(dtype)) return PMI_ERR_ARG;
-  BY_DTYPE(rn_stage_input_kernel, dim3(grid_for((int64_t)N * H * W)), img, mean, stdv, (u16*)out, N, H * W);
+  BY_DTYPE(rn_stage_input_kernel, dim3(grid_256((int64_t)N * H * W)), img, mean, stdv, (u16*)out, N, H * W);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 
 extern "C" int pmi_rn_stage_input_bwd(const float* dx, int ldc, const float* stdv, float* dimg, int N, int H, int W, float mul, pmi_stream_t s) {
   if (!dx || !stdv || !dimg || N <= 0 || H <= 0 || W <= 0 || ldc < 3) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(rn_stage_input_bwd_kernel, dim3(grid_for((int64_t)N * 3 * H * W)), dim3(256), 0, ST, dx, ldc, stdv, dimg, N, H * W, mul);
+  hipLaunchKernelGGL(rn_stage_input_bwd_kernel, dim3(grid_256((int64_t)N * 3 * H * W)), dim3(256), 0, ST, dx, ldc, stdv, dimg, N, H * W, mul);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 
 extern "C" int pmi_rn_tokens(const void* x, const float* pos, void* tok, int N, int HW, int C, int dtype, pmi_stream_t s) {
   if (!x || !pos || !tok || N <= 0 || HW <= 0 || C <= 0 || (C & 7) || !RN_DTYPE_OK(dtype)) return PMI_ERR_ARG;
-  BY_DTYPE(rn_tokens_kernel, dim3(grid_for((int64_t)N * (HW + 1) * (C / 8))), (const u16*)x, pos, (u16*)tok, N, HW, C);
+  BY_DTYPE(rn_tokens_kernel, dim3(grid_256((int64_t)N * (HW + 1) * (C / 8))), (const u16*)x, pos, (u16*)tok, N, HW, C);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
 
 extern "C" int pmi_rn_tokens_bwd(const void* dtok, const float* dq0, void* dx, int N, int HW, int C, int dtype, pmi_stream_t s) {
   if (!dtok || !dx || N <= 0 || HW <= 0 || C <= 0 || (C & 7) || !RN_DTYPE_OK(dtype)) return PMI_ERR_ARG;
-  BY_DTYPE(rn_tokens_bwd_kernel, dim3(grid_for((int64_t)N * HW * (C / 8))), (const u16*)dtok, dq0, (u16*)dx, N, HW, C);
+  BY_DTYPE(rn_tokens_bwd_kernel, dim3(grid_256((int64_t)N * HW * (C / 8))), (const u16*)dtok, dq0, (u16*)dx, N, HW, C);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }

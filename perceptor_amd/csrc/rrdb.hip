@@ -18,6 +18,7 @@
 // halo read and no store crosses an image boundary.
 #include "../../include/perceptor_hip.h"
 #include "common.h"
+#include "launch_util.h"
 
 namespace {
 
@@ -118,8 +119,6 @@ __global__ __launch_bounds__(256) void rdb_conv_kernel(const u16* X, int ldx, in
     }
   }
 }
-
-inline bool finite_f(float v) { return v == v && v - v == 0.f; }
 
 }  // namespace
 

@@ -9,6 +9,7 @@
 // All of it is HBM/L2-bound integer and elementwise work: coalesced 4-byte streams, LDS histograms, no MFMA.
 #include "../../include/perceptor_hip.h"
 #include "common.h"
+#include "launch_util.h"
 
 namespace {
 
@@ -437,10 +438,6 @@ extern "C" int pmi_clamp_grad(const float* x, const float* grad, const float* lo
   return PMI_OK;
 }
 
-static inline int edm_grid(int64_t work) {
-  const int64_t b = (work + 255) / 256;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
 static inline bool edm_count_ok(int count, int N) { return count == 1 || count == N; }
 
 extern "C" int pmi_edm_stage_in(const float* img, const float* sigma, int sigma_n, float sigma_data, void* x, float* c_noise, int N, int H, int W,
@@ -448,7 +445,7 @@ extern "C" int pmi_edm_stage_in(const float* img, const float* sigma, int sigma_
   if (!img || !sigma || !x || !c_noise || N <= 0 || H <= 0 || W <= 0 || Cpad < 8 || (Cpad & 7) || !edm_count_ok(sigma_n, N) || !(sigma_data > 0.f) ||
       (dtype != PMI_DT_F16 && dtype != PMI_DT_BF16) || ((uintptr_t)x & 15))
     return PMI_ERR_ARG;
-  dim3 grid(edm_grid((int64_t)N * H * W * (Cpad / 8))), block(256);
+  dim3 grid(grid_256((int64_t)N * H * W * (Cpad / 8))), block(256);
   if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(edm_stage_in_kernel<BF16>, grid, block, 0, ST, img, sigma, sigma_n, sigma_data, (u16*)x, c_noise, N, H * W, Cpad);
   else hipLaunchKernelGGL(edm_stage_in_kernel<F16>, grid, block, 0, ST, img, sigma, sigma_n, sigma_data, (u16*)x, c_noise, N, H * W, Cpad);
   PMI_CHECK_LAUNCH();
@@ -458,7 +455,7 @@ extern "C" int pmi_edm_stage_in(const float* img, const float* sigma, int sigma_
 extern "C" int pmi_edm_stage_out(const float* img, const float* net_out, int ld, const float* sigma, int sigma_n, float sigma_data, float* denoised_xs,
                                  int N, int H, int W, pmi_stream_t s) {
   if (!img || !net_out || !sigma || !denoised_xs || N <= 0 || H <= 0 || W <= 0 || ld < 3 || !edm_count_ok(sigma_n, N) || !(sigma_data > 0.f)) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(edm_stage_out_kernel, dim3(edm_grid((int64_t)N * 3 * H * W)), dim3(256), 0, ST, img, net_out, ld, sigma, sigma_n, sigma_data, denoised_xs, N, H * W);
+  hipLaunchKernelGGL(edm_stage_out_kernel, dim3(grid_256((int64_t)N * 3 * H * W)), dim3(256), 0, ST, img, net_out, ld, sigma, sigma_n, sigma_data, denoised_xs, N, H * W);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
@@ -469,7 +466,7 @@ extern "C" int pmi_edm_predict(const float* img, const float* denoised_xs, const
   if (!img || !denoised_xs || !sigma || N <= 0 || chw <= 0 || !edm_count_ok(sigma_n, N) || (!eps_out && !step_out && !corr_out)) return PMI_ERR_ARG;
   if (step_out && (!sigma_to || !edm_count_ok(sigma_to_n, N))) return PMI_ERR_ARG;
   if (corr_out && (!prev_img || !prev_sigma || !prev_eps || !edm_count_ok(prev_sigma_n, N))) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(edm_predict_kernel, dim3(edm_grid(N * chw)), dim3(256), 0, ST, img, denoised_xs, sigma, sigma_n, sigma_to, sigma_to_n, prev_img,
+  hipLaunchKernelGGL(edm_predict_kernel, dim3(grid_256(N * chw)), dim3(256), 0, ST, img, denoised_xs, sigma, sigma_n, sigma_to, sigma_to_n, prev_img,
                      prev_sigma, prev_sigma_n, prev_eps, eps_out, step_out, corr_out, N, chw);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
@@ -478,7 +475,7 @@ extern "C" int pmi_edm_predict(const float* img, const float* denoised_xs, const
 extern "C" int pmi_edm_inject_noise(const float* img, const float* sigma, int sigma_n, const float* sigma_rev, int sigma_rev_n, const float* noise,
                                     float s_noise, float* out, int N, int64_t chw, pmi_stream_t s) {
   if (!img || !sigma || !sigma_rev || !noise || !out || N <= 0 || chw <= 0 || !edm_count_ok(sigma_n, N) || !edm_count_ok(sigma_rev_n, N)) return PMI_ERR_ARG;
-  hipLaunchKernelGGL(edm_inject_noise_kernel, dim3(edm_grid(N * chw)), dim3(256), 0, ST, img, sigma, sigma_n, sigma_rev, sigma_rev_n, noise, s_noise, out, N, chw);
+  hipLaunchKernelGGL(edm_inject_noise_kernel, dim3(grid_256(N * chw)), dim3(256), 0, ST, img, sigma, sigma_n, sigma_rev, sigma_rev_n, noise, s_noise, out, N, chw);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }
@@ -492,7 +489,7 @@ extern "C" int pmi_edm_lms(const float* img, const float* eps0, const float* eps
   edm_lms_terms t;
   const float c[4] = {coeff0, coeff1, coeff2, coeff3};
   for (int k = 0; k < 4; ++k) { t.eps[k] = k < order ? e[k] : nullptr; t.coeff[k] = k < order ? c[k] : 0.f; }
-  hipLaunchKernelGGL(edm_lms_kernel, dim3(edm_grid(total)), dim3(256), 0, ST, img, t, order, out, total);
+  hipLaunchKernelGGL(edm_lms_kernel, dim3(grid_256(total)), dim3(256), 0, ST, img, t, order, out, total);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }

@@ -13,6 +13,7 @@
 // T workspace) are both K-contiguous, staged through the LDS with coalesced 16-byte loads.
 #include "../../include/perceptor_hip.h"
 #include "common.h"
+#include "launch_util.h"
 
 namespace {
 
@@ -21,14 +22,6 @@ constexpr int GT = 64;               // Gram output tile (rows and columns) per 
 constexpr int GK = 64;               // pixels per staged K step
 constexpr int GLD = GK + 8;          // LDS row pitch in elements: 144 bytes, 16-byte aligned rows
 constexpr int GRAM_MAX_SPLITS = 32;
-
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // ------------------------------------------------------------------------------------------------------------------ max pool
 // one thread: 8 channels of one 2x2 window
@@ -317,10 +310,6 @@ inline bool level_args_ok(int N, int HW, int C) {
 inline bool pool_args_ok(int N, int H, int W, int C) {
   return N > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0 && (int64_t)N * H * W * C < ((int64_t)1 << 40);
 }
-inline unsigned slots_for(int64_t units) {
-  const int64_t nb = (units + 255) / 256;
-  return (unsigned)(nb < 1 ? 1 : (nb > SLOTS ? SLOTS : nb));
-}
 
 }  // namespace
 
@@ -370,7 +359,7 @@ extern "C" int pmi_style_level(const void* fa, const void* fb, const float* Ga, 
   if (!fa || !fb || !Ga || !Gb || !S || !loss2 || !partial || !level_args_ok(N, HW, C) || (dtype != PMI_DT_F16 && dtype != PMI_DT_BF16))
     return PMI_ERR_ARG;
   const int64_t count = (int64_t)N * HW * C, R = (int64_t)N * C;
-  const unsigned n0 = slots_for(count / 8), n1 = slots_for(R * R / 4);
+  const unsigned n0 = grid_256(count / 8, SLOTS), n1 = grid_256(R * R / 4, SLOTS);
   BY_DTYPE(feat_l1_kernel, dim3(n0), (const u16*)fa, (const u16*)fb, partial, count / 8);
   BY_DTYPE(gram_l1_sign_kernel, dim3(n1), Ga, Gb, (u16*)S, partial + SLOTS, R * R / 4);
   hipLaunchKernelGGL(level_final_kernel, dim3(1), dim3(SLOTS), 0, ST, partial, (int)n0, (int)n1, loss2, (float)(1.0 / (double)count),

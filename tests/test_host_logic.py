@@ -276,3 +276,21 @@ def test_f16_grad_scale_rule():
     assert f16_grad_scale([1e-3, nan]) == 1.0 and f16_grad_scale([nan, 1e-3]) == 1.0   # a NaN in any sample
     assert f16_grad_scale([1e-3, inf]) == 1.0
     assert f16_grad_scale([1e-30]) == 2.0 ** 24 and f16_grad_scale([1e30]) == 2.0 ** -24
+
+
+def test_every_included_header_is_a_build_dependency():
+    """build.build() recompiles an object when any file of headers() is newer: every quoted #include in csrc/ must be one of them."""
+    import os
+    import re
+    from perceptor_amd.csrc import build
+    deps = {os.path.realpath(h) for h in build.headers()}
+    assert all(os.path.isfile(h) for h in deps)
+    seen = 0
+    for name in sorted(os.listdir(build.HERE)):
+        if not name.endswith((".hip", ".h")):
+            continue
+        with open(os.path.join(build.HERE, name)) as f:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), flags=re.M):
+                seen += 1
+                assert os.path.realpath(os.path.join(build.HERE, inc)) in deps, f"{name} includes {inc}, which build.headers() does not list"
+    assert seen >= 2 * len(build.SOURCES)            # each source includes at least the public header and common.h
