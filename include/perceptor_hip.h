@@ -499,16 +499,30 @@ int pmi_rdb_conv3x3(const void* X, int ldx, int Cin, const void* Wp, const float
  *   >= 2 -> [N, H/2, W/2, C].  up: reflect-pad 1, conv_transpose2d with (2k)(2k)^T, stride 2, padding 3, H and W >= 2 -> [N, 2H, 2W, C]; per
  *   axis out[2y] = x[refl(y-1)]/4 + 3x[y]/4, out[2y+1] = 3x[y]/4 + x[refl(y+1)]/4 (refl: x[-1] = x[1], x[H] = x[H-2]).  fp32 sums, one
  *   rounding at the store.  Any other shape or dtype: PMI_ERR_ARG, nothing written.
+ * pmi_fir_down2_bwd / pmi_fir_up2_bwd: their exact transposes, reflection included (the input gradient).  H, W are the FORWARD input's size:
+ *   both write dx [N, H, W, C]; dy is [N, H/2, W/2, C] (down_bwd, H and W even) resp. [N, 2H, 2W, C] (up_bwd).  Gather form, no atomics: per
+ *   axis at most 3 resp. 6 terms (the folds of the padded samples land on rows 1 and H-2), fp32 sums of exact products, one rounding at the
+ *   store, two runs bit-equal.  Same contract as the forward pair.
  * pmi_edm_*: fp32 NCHW images in [0, 1] (x = 2 img - 1), sigma one value per sample (count N) or one for the batch (count 1); D = sigma_data.
  *   stage_in:  x16 [N, H, W, Cpad] = c_in(sigma) x (channels 3.. zero), c_in = 1 / sqrt(D^2 + sigma^2); c_noise [sigma_n] = ln(sigma) / 4.
  *   stage_out: denoised_xs = c_skip x + c_out F, c_skip = D^2 / (D^2 + sigma^2), c_out = sigma D / sqrt(D^2 + sigma^2); F = net_out fp32 NHWC,
  *              ld values per pixel.
- *   predict:   eps = (x - denoised_xs) / sigma; step = decode(denoised_xs + eps sigma_to); corr = decode(x_prev + (sigma - sigma_prev)
+ *   stage_out_bwd: g16 [N, H, W, Cpad] = (scale c_out) d_denoised (channels 3.. zero) from d_denoised fp32 NCHW [N, 3, H, W]; scale > 0 is the
+ *              caller's power of two that keeps an f16 gradient in range (1 for bf16).
+ *   stage_in_bwd: d_images = 2 (c_skip d_denoised + (c_in inv_scale) gx) fp32 NCHW; gx = the fp32 NHWC gradient wrt the network input, ld
+ *              values per pixel, still scaled; the 2 is x = 2 img - 1.  The gradient wrt sigma is not computed.
+ *   predict:  eps = (x - denoised_xs) / sigma; step = decode(denoised_xs + eps sigma_to); corr = decode(x_prev + (sigma - sigma_prev)
  *              (eps + eps_prev) / 2); decode(x) = (x + 1) / 2.  Each output may be NULL (at least one is not); an output's inputs must be given.
  *   inject_noise: decode(x + sqrt(sigma_rev^2 - sigma^2) noise s_noise).
  *   lms:       decode(x + sum_{k < order} coeff_k eps_k), order 1..4, over `total` elements. */
 int pmi_fir_down2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);
 int pmi_fir_up2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_fir_down2_bwd(const void* dy, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_fir_up2_bwd(const void* dy, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_edm_stage_out_bwd(const float* d_denoised, const float* sigma, int sigma_n, float sigma_data, float scale, void* g, int N, int H,
+                          int W, int Cpad, int dtype, pmi_stream_t s);
+int pmi_edm_stage_in_bwd(const float* d_denoised, const float* gx, int ld, const float* sigma, int sigma_n, float sigma_data,
+                         float inv_scale, float* d_images, int N, int H, int W, pmi_stream_t s);
 int pmi_edm_stage_in(const float* img, const float* sigma, int sigma_n, float sigma_data, void* x, float* c_noise, int N, int H, int W,
                      int Cpad, int dtype, pmi_stream_t s);
 int pmi_edm_stage_out(const float* img, const float* net_out, int ld, const float* sigma, int sigma_n, float sigma_data, float* denoised_xs,

@@ -184,6 +184,10 @@ _PROTOS = {
     # MonsterDiffusion: FIR resamplers (fir.hip), EDM parameterisation and sampler updates (sampling.hip)
     "pmi_fir_down2": ([_P, _P, _I, _I, _I, _I, _I, _P],),
     "pmi_fir_up2": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_fir_down2_bwd": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_fir_up2_bwd": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_edm_stage_out_bwd": ([_P, _P, _I, _F, _F, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_edm_stage_in_bwd": ([_P, _P, _I, _P, _I, _F, _F, _P, _I, _I, _I, _P],),
     "pmi_edm_stage_in": ([_P, _P, _I, _F, _P, _P, _I, _I, _I, _I, _I, _P],),
     "pmi_edm_stage_out": ([_P, _P, _I, _P, _I, _F, _P, _I, _I, _I, _P],),
     "pmi_edm_predict": ([_P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _L, _P],),

@@ -73,6 +73,73 @@ __global__ __launch_bounds__(256) void fir_up2_kernel(const u16* __restrict__ x,
   }
 }
 
+// ---- adjoints (the input gradient of MonsterEngine) -------------------------------------------------------------------------------------
+// Exact transposes of the two operators above, reflection included, in gather form: one thread per dx pixel and 8 channels, no atomics.
+// Per axis an input index i receives a fixed set of taps, held as (index, weight) slots whose weight is 0 where the tap does not exist:
+//   down (H even, Ho = H / 2; weights over 8):  3 dy[i >> 1];  1 dy[i odd ? (i + 1) / 2 : i / 2 - 1] where that output exists;
+//                                               the folds: 1 dy[0] into i = 1 (padded -1), 1 dy[Ho - 1] into i = H - 2 (padded H)
+//   up   (dy has 2H rows; weights over 4):      3 dy[2i], 3 dy[2i + 1];  1 dy[2i + 2] (i < H - 1), 1 dy[2i - 1] (i > 0);
+//                                               the folds: 1 dy[0] into i = 1, 1 dy[2H - 1] into i = H - 2 (both at H = 3: six terms)
+// The 2-D operator is the outer product; every weight (1, 3, 9 over 64 resp. 16) times a 16-bit value is exact in fp32.
+struct tap { int idx; float w; };
+
+__device__ __forceinline__ void down_bwd_taps(int i, int n, tap t[3]) {
+  const int no = n >> 1, odd = i & 1;
+  t[0].idx = i >> 1; t[0].w = 3.f;
+  const int o1 = odd ? (i + 1) >> 1 : (i >> 1) - 1;
+  const bool v1 = o1 >= 0 && o1 < no;
+  t[1].idx = v1 ? o1 : 0; t[1].w = v1 ? 1.f : 0.f;
+  const bool f0 = i == 1, f1 = i == n - 2;                   // never both: n is even
+  t[2].idx = f1 ? no - 1 : 0; t[2].w = (f0 || f1) ? 1.f : 0.f;
+}
+
+__device__ __forceinline__ void up_bwd_taps(int i, int n, tap t[6]) {
+  t[0].idx = 2 * i; t[0].w = 3.f;
+  t[1].idx = 2 * i + 1; t[1].w = 3.f;
+  t[2].idx = i < n - 1 ? 2 * i + 2 : 0; t[2].w = i < n - 1 ? 1.f : 0.f;
+  t[3].idx = i > 0 ? 2 * i - 1 : 0; t[3].w = i > 0 ? 1.f : 0.f;
+  t[4].idx = 0; t[4].w = i == 1 ? 1.f : 0.f;
+  t[5].idx = 2 * n - 1; t[5].w = i == n - 2 ? 1.f : 0.f;
+}
+
+// dy [N, Hs, Ws, C] -> dx [N, H, W, C]; UP: Hs = 2H with six slots per axis and weights over 16, else Hs = H / 2, three slots, over 64
+template <typename T, bool UP>
+__global__ __launch_bounds__(256) void fir_bwd_kernel(const u16* __restrict__ dy, u16* __restrict__ dx, int N, int H, int W, int C) {
+  constexpr int S = UP ? 6 : 3;
+  constexpr float unit = UP ? 0.0625f : 0.015625f;
+  const int C8 = C >> 3, Hs = UP ? 2 * H : H / 2, Ws = UP ? 2 * W : W / 2;
+  const int64_t total = (int64_t)N * H * W * C8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c8 = (int)(i % C8);
+    const int64_t pix = i / C8;
+    const int n = (int)(pix / ((int64_t)H * W));
+    const int rem = (int)(pix - (int64_t)n * H * W);
+    const int iy = rem / W, ix = rem - iy * W;
+    tap ty[S], tx[S];
+    if (UP) { up_bwd_taps(iy, H, ty); up_bwd_taps(ix, W, tx); }
+    else { down_bwd_taps(iy, H, ty); down_bwd_taps(ix, W, tx); }
+    const u16* b = dy + (int64_t)n * Hs * Ws * C + c8 * 8;
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = 0.f;
+#pragma unroll
+    for (int r = 0; r < S; ++r) {
+      if (ty[r].w == 0.f) continue;
+      const u16* row = b + (int64_t)ty[r].idx * Ws * C;
+#pragma unroll
+      for (int t = 0; t < S; ++t) {
+        if (tx[t].w == 0.f) continue;
+        float f[8];
+        unpack8<T>(*(const uint4*)(row + (int64_t)tx[t].idx * C), f);
+        const float wgt = ty[r].w * tx[t].w * unit;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] += wgt * f[e];
+      }
+    }
+    *(uint4*)(dx + pix * C + c8 * 8) = pack8<T>(o);
+  }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)s)
@@ -95,4 +162,23 @@ extern "C" int pmi_fir_up2(const void* x, void* y, int N, int H, int W, int C, i
   else hipLaunchKernelGGL(fir_up2_kernel<F16>, grid, block, 0, ST, (const u16*)x, (u16*)y, N, H, W, C);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
+}
+
+template <bool UP>
+static int fir_bwd(const void* dy, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
+  if (!dy || !dx || N <= 0 || H < 2 || W < 2 || (!UP && ((H & 1) || (W & 1))) || C <= 0 || (C & 7) || (dtype != PMI_DT_F16 && dtype != PMI_DT_BF16)) return PMI_ERR_ARG;
+  if ((((uintptr_t)dy | (uintptr_t)dx) & 15)) return PMI_ERR_ARG;
+  dim3 grid(grid_256((int64_t)N * H * W * (C / 8))), block(256);
+  if (dtype == PMI_DT_BF16) hipLaunchKernelGGL((fir_bwd_kernel<BF16, UP>), grid, block, 0, ST, (const u16*)dy, (u16*)dx, N, H, W, C);
+  else hipLaunchKernelGGL((fir_bwd_kernel<F16, UP>), grid, block, 0, ST, (const u16*)dy, (u16*)dx, N, H, W, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_fir_down2_bwd(const void* dy, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
+  return fir_bwd<false>(dy, dx, N, H, W, C, dtype, s);
+}
+
+extern "C" int pmi_fir_up2_bwd(const void* dy, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
+  return fir_bwd<true>(dy, dx, N, H, W, C, dtype, s);
 }

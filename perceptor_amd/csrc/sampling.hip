@@ -317,6 +317,48 @@ __global__ __launch_bounds__(256) void edm_stage_out_kernel(const float* __restr
   }
 }
 
+// stage-out adjoint: the gradient entering the network, scale * c_out * d_denoised as 16-bit NHWC (3 channels + zeros to Cpad); c_out as above,
+// then (scale * c_out) * d: one rounding to 16 bit.  scale is the caller's power of two for f16 (1 for bf16)
+template <typename T>
+__global__ __launch_bounds__(256) void edm_stage_out_bwd_kernel(const float* __restrict__ dd, const float* __restrict__ sigma, int sn, float sd,
+                                                                float scale, u16* __restrict__ g, int N, int HW, int Cpad) {
+  const int C8 = Cpad >> 3;
+  const int64_t total = (int64_t)N * HW * C8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c8 = (int)(i % C8);
+    const int64_t pix = i / C8;
+    const int n = (int)(pix / HW);
+    const int64_t p = pix - (int64_t)n * HW;
+    const float sg = edm_sigma(sigma, sn, n);
+    const float c_out = sg * sd / sqrtf(sd * sd + sg * sg);
+    const float k = scale * c_out;
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = c8 * 8 + e;
+      f[e] = c < 3 ? k * dd[((int64_t)n * 3 + c) * HW + p] : 0.f;
+    }
+    *(uint4*)(g + pix * Cpad + c8 * 8) = pack8<T>(f);
+  }
+}
+
+// stage-in adjoint: d_images = 2 * (c_skip * d_denoised + (c_in * inv_scale) * gx) from the fp32 NHWC gradient gx wrt the network input
+// (ld values per pixel, still carrying the caller's scale); the 2 is x = 2 img - 1
+__global__ __launch_bounds__(256) void edm_stage_in_bwd_kernel(const float* __restrict__ dd, const float* __restrict__ gx, int ld,
+                                                               const float* __restrict__ sigma, int sn, float sd, float inv_scale,
+                                                               float* __restrict__ out, int N, int HW) {
+  const int64_t total = (int64_t)N * 3 * HW;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t p = i % HW;
+    const int64_t nc = i / HW;
+    const int c = (int)(nc % 3), n = (int)(nc / 3);
+    const float sg = edm_sigma(sigma, sn, n);
+    const float s2 = sd * sd + sg * sg;
+    const float c_skip = sd * sd / s2, c_in = 1.f / sqrtf(s2);
+    out[i] = 2.f * (c_skip * dd[i] + (c_in * inv_scale) * gx[((int64_t)n * HW + p) * ld + c]);
+  }
+}
+
 // PredictionBatch.eps / .step / .correction from one read of (diffused image, denoised_xs); each output is optional:
 //   eps  = (x - denoised) / sigma
 //   step = decode(denoised + eps * sigma_to)
@@ -456,6 +498,27 @@ extern "C" int pmi_edm_stage_out(const float* img, const float* net_out, int ld,
                                  int N, int H, int W, pmi_stream_t s) {
   if (!img || !net_out || !sigma || !denoised_xs || N <= 0 || H <= 0 || W <= 0 || ld < 3 || !edm_count_ok(sigma_n, N) || !(sigma_data > 0.f)) return PMI_ERR_ARG;
   hipLaunchKernelGGL(edm_stage_out_kernel, dim3(grid_256((int64_t)N * 3 * H * W)), dim3(256), 0, ST, img, net_out, ld, sigma, sigma_n, sigma_data, denoised_xs, N, H * W);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_edm_stage_out_bwd(const float* d_denoised, const float* sigma, int sigma_n, float sigma_data, float scale, void* g, int N, int H,
+                                     int W, int Cpad, int dtype, pmi_stream_t s) {
+  if (!d_denoised || !sigma || !g || N <= 0 || H <= 0 || W <= 0 || Cpad < 8 || (Cpad & 7) || !edm_count_ok(sigma_n, N) || !(sigma_data > 0.f) ||
+      !(scale > 0.f) || (dtype != PMI_DT_F16 && dtype != PMI_DT_BF16) || ((uintptr_t)g & 15)) return PMI_ERR_ARG;
+  dim3 grid(grid_256((int64_t)N * H * W * (Cpad / 8))), block(256);
+  if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(edm_stage_out_bwd_kernel<BF16>, grid, block, 0, ST, d_denoised, sigma, sigma_n, sigma_data, scale, (u16*)g, N, H * W, Cpad);
+  else hipLaunchKernelGGL(edm_stage_out_bwd_kernel<F16>, grid, block, 0, ST, d_denoised, sigma, sigma_n, sigma_data, scale, (u16*)g, N, H * W, Cpad);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_edm_stage_in_bwd(const float* d_denoised, const float* gx, int ld, const float* sigma, int sigma_n, float sigma_data,
+                                    float inv_scale, float* d_images, int N, int H, int W, pmi_stream_t s) {
+  if (!d_denoised || !gx || !sigma || !d_images || N <= 0 || H <= 0 || W <= 0 || ld < 3 || !edm_count_ok(sigma_n, N) || !(sigma_data > 0.f) ||
+      !(inv_scale > 0.f)) return PMI_ERR_ARG;
+  hipLaunchKernelGGL(edm_stage_in_bwd_kernel, dim3(grid_256((int64_t)N * 3 * H * W)), dim3(256), 0, ST, d_denoised, gx, ld, sigma, sigma_n, sigma_data,
+                     inv_scale, d_images, N, H * W);
   PMI_CHECK_LAUNCH();
   return PMI_OK;
 }

@@ -12,6 +12,10 @@ head-dim-64 attention in the (q, k, v)-then-heads channel order (one narrower he
 fewer than 64 channels) -> 1x1 out + residual.  Downsample2d / Upsample2d are the FIR kernels of
 csrc/fir.hip.  c_in * x, c_noise and c_skip * x + c_out * F are the pmi_edm_stage_* kernels; the conditioning (Fourier features, mapping
 network, AdaGN mappers) stays fp32.  Nothing inside an evaluation synchronises with the host.
+
+Input gradient (what autograd gives the reference for a loss on the predictions): forward_train() is forward() with a tape, backward() walks
+it in reverse through the transposed convolutions, pmi_gn_bwd_*, the attention backward, the FIR adjoints pmi_fir_*_bwd and the EDM staging
+adjoints pmi_edm_stage_*_bwd.  Weights, sigma and the augmentations are not differentiated.
 """
 from __future__ import annotations
 
@@ -244,64 +248,93 @@ class MonsterEngine:
         return ops.linear_f32(h, *self.map[1], act=ACT_GELU)
 
     # ---- blocks ------------------------------------------------------------------------------------------------------------------
-    def _adagn(self, x, x1, c, off, mod, act):
+    def _adagn(self, x, x1, c, off, mod, act, keep=None):
         # mod has one row when sigma is one value for the batch: film_ld = 0 then reads that row for every sample
-        return ops.group_norm(x, None, None, max(1, c // GROUP_SIZE), self.dt, x1=x1, film=mod[:, off:],
-                              film_ld=mod.stride(0) if mod.shape[0] > 1 else 0, act=act)
+        groups, film, ld = max(1, c // GROUP_SIZE), mod[:, off:], (mod.stride(0) if mod.shape[0] > 1 else 0)
+        if keep is None:
+            return ops.group_norm(x, None, None, groups, self.dt, x1=x1, film=film, film_ld=ld, act=act)
+        # training mode: the launches of ops.group_norm, with the (ca, cb, parts) of the coefficients kept for group_norm_backward
+        gn = ops.group_norm_coeffs_train(x, None, None, groups, self.dt, x1=x1, film=film, film_ld=ld)
+        n, hh, ww, c0 = x.shape
+        y = torch.empty((n, hh, ww, c), dtype=x.dtype, device=x.device)
+        call("pmi_gn_apply", ptr(x), ptr(x1), c0, ptr(gn[0]), ptr(gn[1]), None, ptr(y), n, hh, ww, c, act, 0, self.dt)
+        keep.append(gn)
+        return y
 
-    def _res(self, l: Res, x, x1, mod):
+    def _res(self, l: Res, x, x1, mod, tape=None):
         w, p = self.w, l.key
+        gns = None if tape is None else []
         skip = ops.igemm(x, w[p + ".skip"], a1=x1) if l.cin != l.cout else x
-        h = self._adagn(x, x1, l.cin, l.mod1, mod, ACT_GELU)
-        h = ops.igemm(h, w[p + ".c1"])
-        h = self._adagn(h, None, l.cmid, l.mod2, mod, ACT_GELU)
+        h = self._adagn(x, x1, l.cin, l.mod1, mod, ACT_GELU, gns)
+        h1 = ops.igemm(h, w[p + ".c1"])
+        h = self._adagn(h1, None, l.cmid, l.mod2, mod, ACT_GELU, gns)
+        if tape is not None:         # no GELU output is kept: pmi_gn_bwd_* recompute act'(a x + b) from the norm's input
+            tape.append(("res", l, x, x1, h1, gns[0], gns[1]))
         return ops.igemm(h, w[p + ".c2"], residual=skip)
 
-    def _attn(self, l: Attn, x, mod):
+    def _attn(self, l: Attn, x, mod, tape=None):
         w, p = self.w, l.key
         n, hh, ww, c = x.shape
-        hn = self._adagn(x, None, c, l.mod, mod, ACT_NONE)
+        gns = None if tape is None else []
+        hn = self._adagn(x, None, c, l.mod, mod, ACT_NONE, gns)
         qkv = ops.igemm(hn.view(n * hh * ww, c), w[p + ".qkv"])
         # heads = max(1, C // 64) as DBlock / UBlock build it: 64-wide heads, or ONE narrower head where a block's last layer leaves the level
         # with fewer than 64 channels; order 1: (q, k, v) first, heads inside
-        a = ops.attention(qkv.view(n, hh * ww, 3 * c), max(1, c // HEAD_SIZE), 1, self.dt)
+        heads = max(1, c // HEAD_SIZE)
+        a = ops.attention(qkv.view(n, hh * ww, 3 * c), heads, 1, self.dt)
+        if tape is not None:
+            # the output above stays the inference kernels' (forward_train returns forward's bits); what the backward kernels need -- the
+            # log-sum-exp and head-major copies at d = 64, the kept probabilities otherwise -- comes from the training-form kernels
+            tape.append(("attn", l, x, gns[0], ops.self_attention_train(qkv, n, hh * ww, heads, self.dt)[1]))
         return ops.igemm(a.view(n * hh * ww, c), w[p + ".out"], residual=x.view(n * hh * ww, c)).view(n, hh, ww, c)
 
-    def _run(self, prog, x, x1, mod):
+    def _run(self, prog, x, x1, mod, tape=None):
+        """The block `prog` on x (and the stored skip x1).  With a tape every layer appends the record _back needs."""
         for l in prog:
             if isinstance(l, Res):
-                x, x1 = self._res(l, x, x1, mod), None
+                x, x1 = self._res(l, x, x1, mod, tape), None
             elif isinstance(l, Attn):
-                x = self._attn(l, x, mod)
+                x = self._attn(l, x, mod, tape)
             elif isinstance(l, Down):
                 x = ops.fir_down2(x, self.dt)
+                if tape is not None:
+                    tape.append(("down",))
             else:
                 x = ops.fir_up2(x, self.dt)
+                if tape is not None:
+                    tape.append(("up",))
         assert x1 is None
         return x
 
-    def network(self, x: torch.Tensor, cond: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+    def network(self, x: torch.Tensor, cond: torch.Tensor, taps: Optional[dict] = None, tape: Optional[dict] = None) -> torch.Tensor:
         """base.Model.forward after its mapping network: x NHWC 16-bit [N, H, W, 8] (3 channels + zeros), cond fp32 [N or 1, feats] ->
-        the fp32 NHWC output [N, H, W, 4] (3 channels + padding).  taps: filled with every block's output (tests)."""
+        the fp32 NHWC output [N, H, W, 4] (3 channels + padding).  taps: filled with every block's output (tests).  tape: filled with
+        `mod` and one record list per d- and u-block (training mode)."""
         mod = ops.linear_f32(cond, self.mod_w, self.mod_b)                          # every AdaGN's (weight | bias) at once
         tap = (lambda k, v: taps.__setitem__(k, v)) if taps is not None else (lambda k, v: None)
+
+        def recs(name):
+            if tape is None:
+                return None
+            return tape.setdefault(name, [])
+
+        if tape is not None:
+            tape["mod"] = mod
         h = ops.igemm(x, self.w["proj_in"])
         tap("proj_in", h)
         skips = []
         for i, prog in enumerate(self.d_blocks):
-            h = self._run(prog, h, None, mod)
+            h = self._run(prog, h, None, mod, recs(f"d{i}"))
             skips.append(h)
             tap(f"d{i}", h)
         for i, prog in enumerate(self.u_blocks):
-            h = self._run(prog, h, skips[len(skips) - 1 - i] if i > 0 else None, mod)
+            h = self._run(prog, h, skips[len(skips) - 1 - i] if i > 0 else None, mod, recs(f"u{i}"))
             tap(f"u{i}", h)
         y = ops.igemm(h, self.w["proj_out"], out_f32=True)
         tap("proj_out", y)
         return y
 
-    @torch.no_grad()
-    def forward(self, images: torch.Tensor, sigma: torch.Tensor, augmentations: Optional[torch.Tensor] = None, taps: Optional[dict] = None) -> torch.Tensor:
-        """images NCHW fp32 in [0, 1]; sigma: fp32 device tensor with one value or one per sample -> denoised_xs NCHW fp32 (denoised_)."""
+    def _evaluate(self, images, sigma, augmentations, taps, tape):
         if not images.is_cuda:
             raise RuntimeError("MonsterEngine runs on a HIP device only (no CPU fallback)")
         if images.ndim != 4 or images.shape[1] != 3:
@@ -319,7 +352,122 @@ class MonsterEngine:
         cond = self.cond(c_noise, augmentations)
         if taps is not None:
             taps["x_in"], taps["c_noise"], taps["cond"] = x, c_noise, cond
-        y = self.network(x, cond, taps)
+        if tape is not None:
+            tape["sigma"] = sigma
+        y = self.network(x, cond, taps, tape)
         out = torch.empty_like(images)
         call("pmi_edm_stage_out", ptr(images), ptr(y), y.shape[-1], ptr(sigma), sigma.numel(), SIGMA_DATA, ptr(out), n, hh, ww)
         return out
+
+    @torch.no_grad()
+    def forward(self, images: torch.Tensor, sigma: torch.Tensor, augmentations: Optional[torch.Tensor] = None, taps: Optional[dict] = None) -> torch.Tensor:
+        """images NCHW fp32 in [0, 1]; sigma: fp32 device tensor with one value or one per sample -> denoised_xs NCHW fp32 (denoised_)."""
+        return self._evaluate(images, sigma, augmentations, taps, None)
+
+    # ---- input gradient ----------------------------------------------------------------------------------------------------------
+    # What autograd gives the reference when a loss on predictions.denoised_images back-propagates to diffused_images: d loss / d images
+    # through c_skip x + c_out F(c_in x), weights frozen.  forward_train() is forward() with a tape; backward() walks it in reverse.  dX of
+    # a convolution is the forward kernel on flipped, transposed weights (ops.packed_dx, built lazily, once, into self.w); AdaGN + GELU goes
+    # back through pmi_gn_bwd_* (gamma = NULL, the FiLM row, erf-GELU's derivative recomputed from the norm's input); the resamplers through
+    # their exact transposes pmi_fir_*_bwd.  Out of scope: the gradient to sigma / ts, the gradient to the augmentations, weight gradients,
+    # and the precise and mixed types (MonsterEngine has neither).
+
+    @torch.no_grad()
+    def forward_train(self, images: torch.Tensor, sigma: torch.Tensor, augmentations: Optional[torch.Tensor] = None):
+        """As forward() -- the same kernels and output bits -- keeping what backward() needs.  Returns (denoised_xs NCHW fp32, tape).
+        The tape holds sigma, `mod` (every AdaGN row) and per layer: a Res its input(s) x, x1, conv1's output and both norms'
+        (ca, cb, parts); an Attn its input, the norm's coefficients and self_attention_train's `saved`.  Not differentiated: sigma / ts, the
+        augmentations, the weights; there is no precise or mixed type."""
+        tape: dict = {}
+        return self._evaluate(images, sigma, augmentations, None, tape), tape
+
+    def _film(self, mod, off):
+        return dict(film=mod[:, off:], film_ld=mod.stride(0) if mod.shape[0] > 1 else 0)
+
+    def _res_back(self, rec, g, sd, mod):
+        _, l, x, x1, h1, gn1, gn2 = rec
+        w, p, dt, dev = self.w, l.key, self.dt, self.device
+        d3 = ops.igemm(g, ops.packed_dx(w, p + ".c2T", sd[p + ".main.6.weight"], dt, dev))
+        d1 = ops.group_norm_backward(h1, d3, *gn2, None, max(1, l.cmid // GROUP_SIZE), dt, act=ACT_GELU, **self._film(mod, l.mod2))[0]
+        d2 = ops.igemm(d1, ops.packed_dx(w, p + ".c1T", sd[p + ".main.2.weight"], dt, dev))
+        if l.cin == l.cout:                                                       # identity skip (never over a concat: check_config)
+            gs = (g, None)
+        elif x1 is None:
+            gs = (ops.igemm(g, ops.packed_dx(w, p + ".skipT", sd[p + ".skip.weight"], dt, dev)), None)
+        else:                                                                     # bias-free 1x1 over cat([x, x1]): one dX per source
+            skw, c0 = sd[p + ".skip.weight"], x.shape[-1]
+            gs = (ops.igemm(g, ops.packed_dx(w, p + ".skipT0", skw[:, :c0], dt, dev)),
+                  ops.igemm(g, ops.packed_dx(w, p + ".skipT1", skw[:, c0:], dt, dev)))
+        return ops.group_norm_backward(x, d2, *gn1, None, max(1, l.cin // GROUP_SIZE), dt, x1=x1, act=ACT_GELU, gadd0=gs[0], gadd1=gs[1],
+                                       **self._film(mod, l.mod1))
+
+    def _attn_back(self, rec, g, sd, mod):
+        _, l, x, gn, saved = rec
+        w, p, dt, dev = self.w, l.key, self.dt, self.device
+        n, hh, ww, c = x.shape
+        t, heads = hh * ww, max(1, c // HEAD_SIZE)
+        g2 = g.reshape(n * t, c)
+        da = ops.igemm(g2, ops.packed_dx(w, p + ".outT", sd[p + ".out_proj.weight"], dt, dev))
+        dqkv = ops.self_attention_backward(saved, da, n, t, heads, dt)
+        dhn = ops.igemm(dqkv, ops.packed_dx(w, p + ".qkvT", sd[p + ".qkv_proj.weight"], dt, dev))
+        return ops.group_norm_backward(x, dhn.view(n, hh, ww, c), *gn, None, max(1, c // GROUP_SIZE), dt, act=ACT_NONE, gadd0=g,
+                                       **self._film(mod, l.mod))[0]
+
+    def _back(self, recs, g, sd, mod):
+        """(gradient wrt the block's input, gradient wrt its stored skip or None) from g = gradient wrt its output."""
+        g1 = None
+        for rec in reversed(recs):
+            assert g1 is None
+            if rec[0] == "res":
+                g, g1 = self._res_back(rec, g, sd, mod)
+            elif rec[0] == "attn":
+                g = self._attn_back(rec, g, sd, mod)
+            elif rec[0] == "down":
+                g = ops.fir_down2_bwd(g, self.dt)
+            else:
+                g = ops.fir_up2_bwd(g, self.dt)
+        return g, g1
+
+    @torch.no_grad()
+    def backward(self, tape, d_denoised: torch.Tensor, state_dict, taps: Optional[dict] = None) -> torch.Tensor:
+        """d loss / d images (NCHW fp32, images in [0, 1]) from d loss / d denoised_xs (NCHW fp32 [N, 3, H, W]) and forward_train()'s tape:
+        pmi_edm_stage_out_bwd -> proj_out^T -> the u-blocks in reverse -> the d-blocks in reverse -> proj_in^T -> pmi_edm_stage_in_bwd.
+        `state_dict`: the network's parameters (reference key names); the transposed packings are built from it on first use.
+        f16 scales the gradient by a power of two from the per-sample maxima of c_out * d_denoised (ops.f16_grad_scale: one host read)
+        and divides it out at the end; bf16 is unscaled and never synchronises with the host.
+        taps: receives `gx` (the fp32 NHWC network-input gradient, scale divided out) and, as d<i> / u<i>, the gradient arriving at every
+        block's input (fp32 NHWC, scale divided out; a two-source u-block's is the concat of both sources' gradients).
+        Not computed: the gradient to sigma / ts, to the augmentations and to the weights; no precise or mixed type."""
+        dev, dt = self.device, self.dt
+        sigma, mod = tape["sigma"], tape["mod"]
+        d = d_denoised.to(device=dev, dtype=torch.float32).contiguous()
+        n = d.shape[0]
+        scale = 1.0
+        if dt == _hip.DT_F16:
+            amax = torch.empty((n,), dtype=torch.float32, device=dev)
+            call("pmi_quantile_abs", ptr(d), ptr(amax), n, d[0].numel(), 1.0)
+            s64 = sigma.double().expand(n) if sigma.numel() == 1 else sigma.double()
+            c_out = s64 * SIGMA_DATA / torch.sqrt(SIGMA_DATA ** 2 + s64 ** 2)
+            scale = ops.f16_grad_scale((amax.double() * c_out).tolist())
+        sd = bare_state_dict(state_dict)
+        w = self.w
+        tap = (lambda k, *v: taps.__setitem__(k, torch.cat([t.float() for t in v if t is not None], dim=-1) / scale)) if taps is not None \
+            else (lambda k, *v: None)
+        g = ops.edm_stage_out_bwd(d, sigma, SIGMA_DATA, scale, dt)
+        g = ops.igemm(g, ops.packed_dx(w, "proj_outT", sd["proj_out.weight"], dt, dev, cin_pad=8))
+        L, pending = len(self.d_blocks), {}
+        for i in reversed(range(L)):
+            g, g1 = self._back(tape[f"u{i}"], g, sd, mod)
+            tap(f"u{i}", g, g1)
+            if g1 is not None:
+                pending[L - 1 - i] = g1                                           # the gradient of the stored skip: d-block L-1-i's output
+        for i in reversed(range(L)):
+            if i in pending:
+                g = ops.add2(g, pending.pop(i), dt)
+            g, g1 = self._back(tape[f"d{i}"], g, sd, mod)
+            assert g1 is None
+            tap(f"d{i}", g)
+        gx = ops.igemm(g, ops.packed_dx(w, "proj_inT", sd["proj_in.weight"], dt, dev), out_f32=True)
+        if taps is not None:
+            taps["gx"] = gx[..., :3] / scale
+        return ops.edm_stage_in_bwd(d, gx, sigma, SIGMA_DATA, 1.0 / scale)

@@ -893,6 +893,38 @@ def upsample_bilinear2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
     return _up2_bwd("pmi_upsample_bilinear2_bwd", "pmi_split_upsample_bilinear2_bwd", g, dt)
 
 
+def fir_down2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
+    """Adjoint of fir_down2 (reflection folds included): [N, H/2, W/2, C] -> [N, H, W, C] (csrc/fir.hip)."""
+    n, h, w, c = g.shape
+    out = _empty((n, 2 * h, 2 * w, c), g.dtype, g.device)
+    call("pmi_fir_down2_bwd", ptr(g), ptr(out), n, 2 * h, 2 * w, c, dt)
+    return out
+
+
+def fir_up2_bwd(g: torch.Tensor, dt: int) -> torch.Tensor:
+    """Adjoint of fir_up2 (reflection folds included): [N, 2H, 2W, C] -> [N, H, W, C] (csrc/fir.hip)."""
+    n, h, w, c = g.shape
+    out = _empty((n, h // 2, w // 2, c), g.dtype, g.device)
+    call("pmi_fir_up2_bwd", ptr(g), ptr(out), n, h // 2, w // 2, c, dt)
+    return out
+
+
+def edm_stage_out_bwd(d_denoised: torch.Tensor, sigma: torch.Tensor, sigma_data: float, scale: float, dt: int, cpad: int = 8) -> torch.Tensor:
+    """Adjoint of pmi_edm_stage_out towards the network: d_denoised NCHW fp32 [N, 3, H, W] -> 16-bit NHWC [N, H, W, cpad] = scale * c_out * d."""
+    n, _, h, w = d_denoised.shape
+    g = _empty((n, h, w, cpad), _hip.TORCH_DTYPE[dt], d_denoised.device)
+    call("pmi_edm_stage_out_bwd", ptr(d_denoised), ptr(sigma), sigma.numel(), sigma_data, scale, ptr(g), n, h, w, cpad, dt)
+    return g
+
+
+def edm_stage_in_bwd(d_denoised: torch.Tensor, gx: torch.Tensor, sigma: torch.Tensor, sigma_data: float, inv_scale: float) -> torch.Tensor:
+    """d_images NCHW fp32 = 2 * (c_skip * d_denoised + c_in * inv_scale * gx[..., :3]); gx: fp32 NHWC gradient wrt the network input."""
+    n, _, h, w = d_denoised.shape
+    out = torch.empty_like(d_denoised)
+    call("pmi_edm_stage_in_bwd", ptr(d_denoised), ptr(gx), gx.shape[-1], ptr(sigma), sigma.numel(), sigma_data, inv_scale, ptr(out), n, h, w)
+    return out
+
+
 def _transpose16(src: torch.Tensor, rows: int, cols: int, ld: int, s_o: int, s_i: int, inner: int, batch: int) -> torch.Tensor:
     """[batch, cols, rows padded to 8] 16-bit: block z = (o, i) of src, [rows, cols] with row pitch ld at element o * s_o + i * s_i, transposed."""
     rp = (rows + 7) // 8 * 8

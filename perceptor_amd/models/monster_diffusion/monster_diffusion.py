@@ -15,9 +15,30 @@ from .prediction import PredictionBatch
 _NAMES = ("all", "tiny-hero")          # the reference's two checkpoints: both the product config at 48 x 48
 
 
+class _Denoised(torch.autograd.Function):
+    """denoised_(diffused_images, ts, augmentations) with an input gradient, as autograd provides upstream (the network is an nn.Module
+    there): forward and backward are MonsterEngine.forward_train / backward.  Weights are frozen; ts and the augmentations get no gradient
+    (denoised_ refuses them when they ask for one)."""
+
+    @staticmethod
+    def forward(ctx, diffused_images, sigma, model, augmentations=None):
+        denoised_xs, tape = model.engine.forward_train(diffused_images, sigma, augmentations)
+        ctx.model, ctx.tape = model, tape
+        return denoised_xs
+
+    @staticmethod
+    def backward(ctx, grad):
+        m = ctx.model
+        return m.engine.backward(ctx.tape, grad.contiguous(), m.network.state_dict()), None, None, None
+
+
 class MonsterDiffusion(torch.nn.Module):
-    def __init__(self, name="all", *, weights="synthetic", checkpoint: Optional[str] = None, dtype="bf16", seed=0, config=None):
+    def __init__(self, name="all", *, weights="synthetic", checkpoint: Optional[str] = None, dtype="bf16", seed=0, config=None,
+                 input_grad: bool = False):
+        """input_grad = True: an input that requires grad (under enabled grad) is evaluated with a tape and a loss on the predictions
+        back-propagates to diffused_images (HIP backward, frozen weights); the default refuses such an input, as before."""
         super().__init__()
+        self.input_grad = bool(input_grad)
         if name not in _NAMES:
             raise ValueError(f"Unknown model name {name}")
         self.name = name
@@ -119,13 +140,18 @@ class MonsterDiffusion(torch.nn.Module):
         nonleaky_augmentations = None are the zeros [N, 9] of the reference."""
         if not torch.is_tensor(diffused_images) or not diffused_images.is_cuda:
             raise RuntimeError("MonsterDiffusion runs on a HIP device only: pass device tensors (perceptor_amd has no CPU fallback)")
-        if torch.is_grad_enabled() and diffused_images.requires_grad:
-            raise NotImplementedError("MonsterDiffusion has no input gradient yet")
+        want_grad = torch.is_grad_enabled() and diffused_images.requires_grad
+        if want_grad and not self.input_grad:
+            raise NotImplementedError("MonsterDiffusion has no input gradient yet: construct it with input_grad=True")
+        if self.input_grad and torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in (ts, nonleaky_augmentations)):
+            raise NotImplementedError("MonsterDiffusion(input_grad=True) differentiates diffused_images only: ts and the augmentations have no gradient")
         if diffused_images.ndim != 4 or diffused_images.shape[1] != settings.INPUT_CHANNELS:
             raise ValueError("diffused_images must be [N, 3, H, W]")
         monster.check_size(self.config, *diffused_images.shape[2:])
         eng = self._need_engine()
         sigma = sampler.edm_sigma(torch.as_tensor(ts) if not isinstance(ts, float) else ts, diffused_images.shape[0], self.device)
+        if want_grad:
+            return _Denoised.apply(diffused_images.to(self.device), sigma, self, nonleaky_augmentations)
         return eng.forward(diffused_images.to(self.device), sigma, nonleaky_augmentations)
 
     def forward(self, diffused_images, ts, nonleaky_augmentations=None):
