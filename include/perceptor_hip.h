@@ -559,6 +559,27 @@ int pmi_lrelu_bwd(const void* g, const void* g2, const void* y, void* dz, int64_
 int pmi_lrelu_add(const void* z, const void* r, void* y, int64_t n, float slope, int dtype, pmi_stream_t s);
 int pmi_mean_f32(const float* x, float* partial, float* out, int64_t n, float scale, pmi_stream_t s);
 
+/* ---- drawers.JPEG: the differentiable JPEG codec (jpeg.hip), fp32, one launch per call ----
+ * Coefficients are the reference's own layout (the drawer's state_dict): y [N][(H/8)(W/8)][8][8], cb and cr [N][(H/16)(W/16)][8][8] (4:2:0),
+ *   blocks row-major over the block grid, the first index inside a block is the row (vertical frequency).  images / out / d_out are NCHW
+ *   [N][3][H][W].  H and W multiples of 16, factor finite and > 0, pointers 16-byte aligned; anything else: PMI_ERR_ARG, nothing written.
+ *   Quantisation tables: Annex K luma TRANSPOSED and chroma with its 4 x 4 corner transposed, as jpeg/utils.py:7-31 builds them.
+ * pmi_jpeg_decode: decompress_jpeg.forward (jpeg/decompression.py:171-189): c * (table * factor) * alpha(u) alpha(v), separable 8 x 8 inverse
+ *   DCT (0.25 sum + 128), block merge, chroma replicated 2 x 2, YCbCr -> RGB with the -128 chroma shift (cancelled against the +128
+ *   algebraically), clamp to [0, 255], / 255.
+ * pmi_jpeg_decode_bwd: its exact adjoint: d_y, d_cb, d_cr (each may be NULL: not computed; all NULL: no launch) from d_out.  The pre-clamp
+ *   value is recomputed with the forward's arithmetic; the gradient passes where 0 < v < 255 and is zero elsewhere (a value exactly at 0 or
+ *   255 passes nothing; torch splits such ties).  2 x 2 sums of the chroma pixel gradient, forward DCT basis, alpha, 0.25, table * factor.
+ *   Gather form, no atomics: a macroblock's six blocks depend on its own 16 x 16 pixels only; two runs are bit-equal, and a sample's result
+ *   does not depend on the batch it is in.
+ * pmi_jpeg_encode: compress_jpeg.forward (jpeg/compression.py:176-188): x 255, RGB -> YCbCr, 2 x 2 mean of the chroma, block split, forward
+ *   DCT with 0.25 alpha(u) alpha(v), / (table * factor), then round_mode 1: diff_round(x) = round(x) + (x - round(x))^3 with round half to
+ *   even (utils.py:34-41), 0: no rounding (the reference's rounding= argument given the identity).  Forward only. */
+int pmi_jpeg_decode(const float* y, const float* cb, const float* cr, float factor, float* out, int N, int H, int W, pmi_stream_t s);
+int pmi_jpeg_decode_bwd(const float* y, const float* cb, const float* cr, float factor, const float* d_out, float* d_y, float* d_cb,
+                        float* d_cr, int N, int H, int W, pmi_stream_t s);
+int pmi_jpeg_encode(const float* images, float factor, int round_mode, float* y, float* cb, float* cr, int N, int H, int W, pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,10 @@ _PROTOS = {
     "pmi_lrelu_bwd": ([_P, _P, _P, _P, _L, _F, _I, _P],),
     "pmi_lrelu_add": ([_P, _P, _P, _L, _F, _I, _P],),
     "pmi_mean_f32": ([_P, _P, _P, _L, _F, _P],),
+    # differentiable JPEG codec of drawers.JPEG (jpeg.hip)
+    "pmi_jpeg_decode": ([_P, _P, _P, _F, _P, _I, _I, _I, _P],),
+    "pmi_jpeg_decode_bwd": ([_P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _P],),
+    "pmi_jpeg_encode": ([_P, _F, _I, _P, _P, _P, _I, _I, _I, _P],),
 }
 
 

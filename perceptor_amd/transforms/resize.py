@@ -39,7 +39,12 @@ def _cubic(x):
         (-0.5 * a3 + 2.5 * a2 - 4.0 * a + 2.0) * ((1.0 < a) & (a <= 2.0)).to(x.dtype)
 
 
-_METHODS = {"lanczos3": (_lanczos3, 6), "cubic": (_cubic, 4)}
+def _linear(x):
+    # the triangle of interpolation_methods.py:65-70: x + 1 on [-1, 0), 1 - x on [0, 1]
+    return (x + 1) * ((-1 <= x) & (x < 0)).to(x.dtype) + (1 - x) * ((0 <= x) & (x <= 1)).to(x.dtype)
+
+
+_METHODS = {"lanczos3": (_lanczos3, 6), "cubic": (_cubic, 4), "linear": (_linear, 2)}
 
 
 @lru_cache(maxsize=64)
@@ -119,7 +124,7 @@ def _apply(x: torch.Tensor, idx, w, axis: int, out_sz: int) -> torch.Tensor:
     return out
 
 
-_RESAMPLE = {"bicubic": "cubic", "cubic": "cubic", "lanczos3": "lanczos3"}
+_RESAMPLE = {"bicubic": "cubic", "cubic": "cubic", "lanczos3": "lanczos3", "linear": "linear", "bilinear": "linear"}
 
 
 def _plan(h: int, w: int, out_shape: Tuple[int, int], resample=None):
@@ -135,8 +140,9 @@ def _plan(h: int, w: int, out_shape: Tuple[int, int], resample=None):
 
 
 def resize(images: torch.Tensor, out_shape: Tuple[int, int], resample=None) -> torch.Tensor:
-    """Forward resize of NCHW fp32 images on the HIP device.  resample: None (the reference's default rule, module doc), "bicubic" or
-    "lanczos3" (the reference's ``resample=`` names, resize_right.py:102-110)."""
+    """Forward resize of NCHW fp32 images on the HIP device.  resample: None (the reference's default rule, module doc), "bicubic",
+    "lanczos3" or "linear" / "bilinear" (the reference's ``resample=`` names, resize_right.py:102-110; the triangle kernel has support 2
+    and, like the others, is antialiased when shrinking and zero padded: not F.interpolate's bilinear)."""
     if not images.is_cuda:
         raise RuntimeError("perceptor_amd.transforms.resize runs on a HIP device only (no CPU fallback)")
     x = images.float().contiguous()
@@ -147,10 +153,10 @@ def resize(images: torch.Tensor, out_shape: Tuple[int, int], resample=None) -> t
     return x
 
 
-def resize_backward(grad_out: torch.Tensor, in_hw: Tuple[int, int]) -> torch.Tensor:
-    """Adjoint of ``resize`` (gradient w.r.t. the input images)."""
+def resize_backward(grad_out: torch.Tensor, in_hw: Tuple[int, int], resample=None) -> torch.Tensor:
+    """Adjoint of ``resize`` (gradient w.r.t. the input images); ``resample`` as given to the forward call."""
     g = grad_out.float().contiguous()
-    method, dims = _plan(in_hw[0], in_hw[1], (g.shape[2], g.shape[3]))
+    method, dims = _plan(in_hw[0], in_hw[1], (g.shape[2], g.shape[3]), resample)
     for _, axis, i, o in reversed(dims):
         _, _, idx_t, w_t = _tables_on(g.device, i, o, method)
         g = _apply(g, idx_t, w_t, axis, i)
