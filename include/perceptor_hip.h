@@ -125,6 +125,9 @@ int pmi_igemm_stats_rows(const pmi_igemm_args* a);
  * 128-column tiles (default 128); key 14 = most query chunks per key tile of pmi_attn_flash_bwd_kv (0 = automatic, 1 = the unsplit key role);
  * key 15 = allow tile config 9, up-sampling conv3x3 by output phase (default 1; 0: the gather route of configs 6 / 7 takes them).
  * key 16 = allow the fused conv2 + skip launch, pmi_conv3x3_skip (default 1; 0: pmi_conv3x3_skip_eligible answers 0 and callers keep the skip GEMM).
+ * key 17 = allow the LDS-resident kernels of pmi_vit_attn_fwd / pmi_vit_attn_bwd (head dim 64, T <= 288: one workgroup per image and head,
+ * no layout passes) (default 1; 0: the fragment-order kernels take every shape).  The route is a function of (T, dtype) only; a call's forward
+ * and backward must run under the same value, as the LDS forward writes only the Q, K, V parts of its workspace.
  * `python bench.py --opt "k=v,..."` sets them for a same-box A/B.
  * The library links no vendor GEMM / BLAS: every kernel it launches is in csrc/. */
 int pmi_set_option(int key, int value);

@@ -528,11 +528,375 @@ __global__ __launch_bounds__(64) void vit_attn_bwd_kernel(const u16* __restrict_
 
 }  // namespace
 
+// =====================================================================================================================
+// LDS-resident route (head dim 64, Tp <= 288: the CLIP ViT towers): one head's whole problem fits a CU's LDS, so a multi-wave workgroup
+// per (image, head) loads its operands ONCE with coalesced 16-byte loads and serves every wave's fragments from LDS.  No layout pass:
+// the forward's load is also the rfrag-ordered write of Q, K, V, and the transposed operands (V^T, dO^T, Q^T, K^T) are the same row
+// images read with ds_read_b64_tr_b16.  Tile order and per-element arithmetic are those of the kernels above, so out, lse and dqkv are
+// bit-identical to theirs.
+//
+// LDS image of a [Tp][64] operand: 32-token tile -> 8 chunk planes of 512 B (chunk = 8 channels = 16 B) -> 32 rows of 16 B, as rfrag, with
+// the row XOR-ed by 4 * (chunk & 3).  Row reads (ds_read_b128: one chunk plane, 32 rows) stay conflict-free under the XOR (a permutation
+// of 4-row blocks inside the plane); a transposed read's 32-lane half takes 4 rows x 4 chunks (chunk & 3 = 0..3), which the XOR spreads
+// over the four 64-byte quarters of the 256-byte bank row instead of stacking them on one (4-way).
+// =====================================================================================================================
+namespace {
+
+constexpr int VL_MAX_TP = 288;      // 4 images of 288 x 128 B + lse + delta = 149,760 B of the 160 KB
+constexpr int VL_FWD_QT = 5;        // query tiles per forward workgroup: a head with more is split over two workgroups (256 CUs, 128 heads)
+constexpr int VL_BWD_WAVES = 9;     // VL_MAX_TP / 32: one key tile (dK, dV role) or one query tile (dQ role) per wave
+
+typedef short vl_s4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ int vl_off(int t, int ch) {      // byte offset of chunk ch (0..7) of token row t in an image
+  return (t >> 5) * 4096 + ch * 512 + (((t & 31) ^ ((ch & 3) << 2)) << 4);
+}
+
+// per-lane parts of the fragment addresses
+struct VlLane {
+  int row0, row1;   // row read, k-step kk even / odd: chunk 2 kk + lhi, row l31
+  int tr;           // transposed read: lane 4q + p of a 16-lane group supplies row q, channels 4p .. 4p + 3 of the group's 4 x 16 block
+  __device__ __forceinline__ VlLane(int lane) {
+    const int l31 = lane & 31, lhi = lane >> 5;
+    row0 = lhi * 512 + ((l31 ^ (lhi << 2)) << 4);
+    row1 = lhi * 512 + ((l31 ^ ((2 + lhi) << 2)) << 4);
+    const int q = (lane >> 2) & 3, p = lane & 3, k = 2 * ((lane >> 4) & 1) + (p >> 1);      // k = chunk & 3
+    tr = k * 512 + ((((4 * lhi) ^ (4 * k)) + q) << 4) + 8 * (p & 1);
+  }
+};
+
+// fragment of k-step kk (channels 16 kk + 8 lhi .. + 7 of row l31) of token tile tb: what rfrag addresses in global memory
+__device__ __forceinline__ uint4 vl_row_frag(const unsigned char* img, const VlLane& L, int tb, int kk) {
+  return *(const uint4*)(img + tb * 4096 + kk * 1024 + ((kk & 1) ? L.row1 : L.row0));
+}
+// transposed fragment (channel 32 db + l31; tokens 16 ks + 4 lhi + {0..3, 8..11} of tile tb): what tfrag addresses in global memory
+__device__ __forceinline__ uint4 vl_tr_frag(const unsigned char* img, const VlLane& L, int tb, int ks, int db) {
+  typedef __attribute__((address_space(3))) vl_s4* lds_s4;
+  const unsigned char* p = img + tb * 4096 + db * 2048 + ks * 256;
+  const vl_s4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(p + L.tr));
+  const vl_s4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(p + (L.tr ^ 128)));       // rows + 8: bit 3 of the row, under the XOR too
+  const uint2 ua = __builtin_bit_cast(uint2, a), ub = __builtin_bit_cast(uint2, b);
+  return make_uint4(ua.x, ua.y, ub.x, ub.y);
+}
+
+// forward: grid (ceil(Tp / 32 / 5), N * heads), 5 waves.  Every workgroup stages the head's K and V (zero rows for t >= T); wave w takes
+// query tile 5 * blockIdx.x + w with its Q fragments straight from qkv.  Q, K, V go to ws16 parts 0..2 in rfrag order on the way.
+template <typename T_>
+__global__ __launch_bounds__(VL_FWD_QT * 64) void vit_attn_fwd_lds_kernel(const u16* __restrict__ qkv, u16* __restrict__ wq, u16* __restrict__ wk,
+                                                                            u16* __restrict__ wv, u16* __restrict__ out, float* __restrict__ lse,
+                                                                            int T, int Tp, int heads, float scale) {
+  extern __shared__ __align__(16) unsigned char vl_smem[];
+  unsigned char* ki = vl_smem;
+  unsigned char* vi = vl_smem + Tp * 128;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
+  int part, bh;
+  head_xcd_remap(part, bh);
+  const int n = bh / heads, h = bh - n * heads, C = heads * 64, ntb = Tp >> 5;
+  const u16* src = qkv + (int64_t)n * T * 3 * C + h * 64;
+  constexpr int NT = VL_FWD_QT * 64, IT = (VL_MAX_TP * 8 + NT - 1) / NT;
+  // 64 consecutive items = 8 rows x 8 chunks with the ROW on the low lane bits: 8 neighbouring lanes write 128 contiguous bytes of one chunk
+  // plane, in LDS (no bank conflict) and in ws16
+  uint4 kr[IT], vr[IT];
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const int e = i * NT + tid, t = (e >> 6) * 8 + (e & 7), ch = (e >> 3) & 7;
+    const u16* p = src + (int64_t)(t < T ? t : T - 1) * 3 * C + ch * 8;      // always a valid row: the loads need no branch, all are in flight together
+    kr[i] = *(const uint4*)(p + C); vr[i] = *(const uint4*)(p + 2 * C);
+    if (t >= T) { kr[i] = make_uint4(0, 0, 0, 0); vr[i] = kr[i]; }
+  }
+  const int bx = part * VL_FWD_QT + wave;
+  const bool active = bx < ntb;                            // wave-uniform
+  const int t0 = bx * 32;
+  uint4 qf[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    const int t = t0 + l31;
+    qf[kk] = *(const uint4*)(src + (int64_t)(t < T ? t : T - 1) * 3 * C + kk * 16 + lhi * 8);
+    if (t >= T) qf[kk] = make_uint4(0, 0, 0, 0);
+  }
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const int e = i * NT + tid, t = (e >> 6) * 8 + (e & 7), ch = (e >> 3) & 7;
+    if (e < Tp * 8) {
+      const int o = vl_off(t, ch);
+      *(uint4*)(ki + o) = kr[i]; *(uint4*)(vi + o) = vr[i];
+      const int64_t g = rfrag(bh, ntb, t >> 5, ch >> 1, ch & 1, t & 31);
+      if (part == 0) *(uint4*)(wk + g) = kr[i];
+      if (part == (int)gridDim.x - 1) *(uint4*)(wv + g) = vr[i];
+    }
+  }
+  if (active) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) *(uint4*)(wq + rfrag(bh, ntb, bx, kk, lhi, l31)) = qf[kk];
+  }
+  __syncthreads();
+  if (!active) return;
+  const VlLane L(lane);
+  f32x16 o0, o1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+  float m_run = -1e30f, l_run = 0.f;
+  for (int sb = 0; sb < ntb; ++sb) {
+    const int s0 = sb * 32;
+    f32x16 sacc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) sacc = T_::mfma32(vl_row_frag(ki, L, sb, kk), qf[kk], sacc);
+    uint4 vt[2][2];
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2)
+#pragma unroll
+      for (int db = 0; db < 2; ++db) vt[k2][db] = vl_tr_frag(vi, L, sb, k2, db);
+    float mx = -1e30f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int s = s0 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+      const float v = s < T ? sacc[r] * scale : -1e30f;
+      sacc[r] = v; mx = fmaxf(mx, v);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx), alpha = __expf(m_run - m_new);
+    float rs = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { const float p = __expf(sacc[r] - m_new); sacc[r] = p; rs += p; }
+    rs += __shfl_xor(rs, 32);
+    l_run = l_run * alpha + rs; m_run = m_new;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {
+      float pf[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pf[j] = sacc[8 * k2 + j];
+      const uint4 pfrag = pack8<T_>(pf);
+      o0 = T_::mfma32(vt[k2][0], pfrag, o0);
+      o1 = T_::mfma32(vt[k2][1], pfrag, o1);
+    }
+  }
+  const int t = t0 + l31;
+  if (lhi == 0) lse[(int64_t)bh * Tp + t] = t < T ? m_run + __logf(l_run) : 0.f;
+  if (t < T) {
+    const float inv = 1.f / l_run;
+    u16* ob = out + ((int64_t)n * T + t) * C + h * 64 + 4 * lhi;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      *(uint2*)(ob + 8 * g) = pack4<T_>(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
+      *(uint2*)(ob + 32 + 8 * g) = pack4<T_>(o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
+    }
+  }
+}
+
+// backward: grid (2, N * heads), 9 waves: two workgroups per head, one per role, so 128 heads fill 256 CUs (one workgroup doing both roles
+// in turn measured 32.2 us against 24.0).  Both stage Q, K, V from ws16 parts 0..2 (one contiguous block per head), dO from the row-major
+// dout, lse from the forward and delta = sum_d dO * O formed while loading (O is not kept); then wave w owns key tile w (role 0: dK, dV over
+// all query tiles, the arithmetic of vit_attn_dkdv_body) or query tile w (role 1: dQ over all key tiles, vit_attn_dq_body), every operand
+// from LDS.  No atomics: each output element has one owner and a fixed accumulation order.
+template <typename T_>
+__global__ __launch_bounds__(VL_BWD_WAVES * 64) void vit_attn_bwd_lds_kernel(const u16* __restrict__ wq, const u16* __restrict__ wk,
+                                                                            const u16* __restrict__ wv, const u16* __restrict__ dout,
+                                                                            const u16* __restrict__ o, const float* __restrict__ lse,
+                                                                            u16* __restrict__ dqkv, int T, int Tp, int heads, float scale) {
+  extern __shared__ __align__(16) unsigned char vl_smem[];
+  unsigned char* qi = vl_smem;
+  unsigned char* ki = qi + Tp * 128;
+  unsigned char* vi = ki + Tp * 128;
+  unsigned char* di = vi + Tp * 128;
+  float* ls = (float*)(di + Tp * 128);
+  float* dl = ls + Tp;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
+  int role, bh;                                           // role 0 = dK, dV, role 1 = dQ; a head's two workgroups run on one XCD
+  head_xcd_remap(role, bh);
+  const int n = bh / heads, h = bh - n * heads, C = heads * 64, ntb = Tp >> 5;
+  constexpr int NT = VL_BWD_WAVES * 64, IT = VL_MAX_TP * 8 / NT;
+  static_assert(IT * NT == VL_MAX_TP * 8, "items per thread");
+  {
+    const uint4* gq = (const uint4*)(wq + (int64_t)bh * Tp * 64);
+    const uint4* gk = (const uint4*)(wk + (int64_t)bh * Tp * 64);
+    const uint4* gv = (const uint4*)(wv + (int64_t)bh * Tp * 64);
+    uint4 a[IT], b[IT], c[IT];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int e = i * NT + tid, ec = e < Tp * 8 ? e : Tp * 8 - 1;      // clamped, not branched: every load is in flight at once
+      a[i] = gq[ec]; b[i] = gk[ec]; c[i] = gv[ec];
+    }
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int e = i * NT + tid;                          // rfrag order: [tile][chunk][row]
+      if (e < Tp * 8) {
+        const int off = vl_off((e >> 8) * 32 + (e & 31), (e >> 5) & 7);
+        *(uint4*)(qi + off) = a[i]; *(uint4*)(ki + off) = b[i]; *(uint4*)(vi + off) = c[i];
+      }
+    }
+  }
+  {
+    const int64_t base = (int64_t)n * T * C + h * 64;
+    uint4 a[IT], b[IT];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int e = i * NT + tid, t = (e >> 6) * 8 + (e & 7), ch = (e >> 3) & 7;
+      const int64_t g = base + (int64_t)(t < T ? t : T - 1) * C + ch * 8;
+      a[i] = *(const uint4*)(dout + g); b[i] = *(const uint4*)(o + g);
+      if (t >= T) { a[i] = make_uint4(0, 0, 0, 0); b[i] = a[i]; }
+    }
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const int e = i * NT + tid, t = (e >> 6) * 8 + (e & 7), ch = (e >> 3) & 7;
+      if (e < Tp * 8) {                                    // wave-uniform: Tp * 8 is a multiple of 64 and so is NT
+        *(uint4*)(di + vl_off(t, ch)) = a[i];
+        float x[8], y[8], p = 0.f;
+        unpack8<T_>(a[i], x); unpack8<T_>(b[i], y);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) p += x[j] * y[j];
+        p += __shfl_xor(p, 8); p += __shfl_xor(p, 16); p += __shfl_xor(p, 32);      // the row's 8 chunks sit 8 lanes apart
+        if (ch == 0) dl[t] = p;
+      }
+    }
+    for (int t = tid; t < Tp; t += NT) ls[t] = lse[(int64_t)bh * Tp + t];
+  }
+  __syncthreads();
+  if (wave >= ntb) return;                                 // wave-uniform, after the only barrier
+  const VlLane L(lane);
+  const int bx = wave;
+  if (role == 0) {  // ---- dK, dV of key tile bx
+    // the tile's own K and V fragments are re-read from LDS per query tile (bxo: opaque, so the reads are not hoisted): held in registers
+    // (32 more) the loop spills at 3 waves per SIMD
+    const bool key_ok = bx * 32 + l31 < T;
+    f32x16 dk0, dk1, dv0, dv1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dk0[r] = 0.f; dk1[r] = 0.f; dv0[r] = 0.f; dv1[r] = 0.f; }
+    for (int tb = 0; tb < ntb; ++tb) {
+      const int t0 = tb * 32;
+      int bxo = bx;
+      asm volatile("" : "+v"(bxo));
+      f32x16 sacc, dp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        sacc = T_::mfma32(vl_row_frag(qi, L, tb, kk), vl_row_frag(ki, L, bxo, kk), sacc);     // rows = queries, lane = key
+        dp = T_::mfma32(vl_row_frag(di, L, tb, kk), vl_row_frag(vi, L, bxo, kk), dp);
+      }
+      float pf[16];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 l4 = *(const float4*)(ls + t0 + 8 * g + 4 * lhi), d4 = *(const float4*)(dl + t0 + 8 * g + 4 * lhi);
+        const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int r = 4 * g + j, t = t0 + 8 * g + 4 * lhi + j;
+          const float p = (key_ok && t < T) ? __expf(sacc[r] * scale - lv[j]) : 0.f;
+          pf[r] = p;
+          sacc[r] = p * (dp[r] - dv[j]) * scale;            // dS[t][s]
+        }
+      }
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const uint4 pfrag = pack8<T_>(pf + 8 * ks);
+        float g[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) g[j] = sacc[8 * ks + j];
+        const uint4 dsf = pack8<T_>(g);
+        dv0 = T_::mfma32(vl_tr_frag(di, L, tb, ks, 0), pfrag, dv0); dk0 = T_::mfma32(vl_tr_frag(qi, L, tb, ks, 0), dsf, dk0);
+        dv1 = T_::mfma32(vl_tr_frag(di, L, tb, ks, 1), pfrag, dv1); dk1 = T_::mfma32(vl_tr_frag(qi, L, tb, ks, 1), dsf, dk1);
+      }
+    }
+    const int s = bx * 32 + l31;
+    if (s < T) {
+      u16* okp = dqkv + ((int64_t)n * T + s) * 3 * C + C + h * 64 + 4 * lhi;       // dK slot
+      u16* ovp = okp + C;                                                           // dV slot
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        *(uint2*)(okp + 8 * g) = pack4<T_>(dk0[4 * g], dk0[4 * g + 1], dk0[4 * g + 2], dk0[4 * g + 3]);
+        *(uint2*)(okp + 32 + 8 * g) = pack4<T_>(dk1[4 * g], dk1[4 * g + 1], dk1[4 * g + 2], dk1[4 * g + 3]);
+        *(uint2*)(ovp + 8 * g) = pack4<T_>(dv0[4 * g], dv0[4 * g + 1], dv0[4 * g + 2], dv0[4 * g + 3]);
+        *(uint2*)(ovp + 32 + 8 * g) = pack4<T_>(dv1[4 * g], dv1[4 * g + 1], dv1[4 * g + 2], dv1[4 * g + 3]);
+      }
+    }
+  } else {  // ---- dQ of query tile bx
+    uint4 qf[4], dof[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) { qf[kk] = vl_row_frag(qi, L, bx, kk); dof[kk] = vl_row_frag(di, L, bx, kk); }
+    const float my_lse = ls[bx * 32 + l31], my_delta = dl[bx * 32 + l31];
+    f32x16 g0, g1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { g0[r] = 0.f; g1[r] = 0.f; }
+    for (int sb = 0; sb < ntb; ++sb) {
+      const int s0 = sb * 32;
+      f32x16 sacc, dp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { sacc[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        sacc = T_::mfma32(vl_row_frag(ki, L, sb, kk), qf[kk], sacc);
+        dp = T_::mfma32(vl_row_frag(vi, L, sb, kk), dof[kk], dp);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int s = s0 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        const float p = s < T ? __expf(sacc[r] * scale - my_lse) : 0.f;
+        sacc[r] = p * (dp[r] - my_delta) * scale;                 // dS^T[s][t]
+      }
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        float g[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) g[j] = sacc[8 * ks + j];
+        const uint4 dsf = pack8<T_>(g);
+        g0 = T_::mfma32(vl_tr_frag(ki, L, sb, ks, 0), dsf, g0);
+        g1 = T_::mfma32(vl_tr_frag(ki, L, sb, ks, 1), dsf, g1);
+      }
+    }
+    const int t = bx * 32 + l31;
+    if (t < T) {
+      u16* ob = dqkv + ((int64_t)n * T + t) * 3 * C + h * 64 + 4 * lhi;        // dQ slot
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        *(uint2*)(ob + 8 * g) = pack4<T_>(g0[4 * g], g0[4 * g + 1], g0[4 * g + 2], g0[4 * g + 3]);
+        *(uint2*)(ob + 32 + 8 * g) = pack4<T_>(g1[4 * g], g1[4 * g + 1], g1[4 * g + 2], g1[4 * g + 3]);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+static int g_vit_lds = 1;        // A/B switch (pmi_set_option 17): 0 = the fragment-order kernels everywhere, 1 = the LDS-resident kernels where eligible
+void pmi_vit_attn_lds(int v) { g_vit_lds = v; }
+
+// THE route rule of pmi_vit_attn_fwd / pmi_vit_attn_bwd (head dim 64): a function of the sequence and the type only, never of N, so a
+// shard and its slice of a larger batch take the same kernels.  Forward and backward of one call must see the same option value: the
+// LDS forward does not write the transposed workspace parts the fragment-order backward reads.
+static bool vit_lds_route(int T, int dtype) {
+  return g_vit_lds && (T + 31) / 32 * 32 <= VL_MAX_TP && (dtype == PMI_DT_BF16 || dtype == PMI_DT_F16);
+}
+
+// more than 64 KB of dynamic LDS needs the limit raised per kernel and device
+template <typename K>
+static bool vl_allow_lds(K kern, int bytes) {
+  static bool done[64] = {};                               // one flag per kernel instantiation and device
+  int dev = 0;
+  if (bytes <= 64 * 1024) return true;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  if (!done[dev]) done[dev] = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+  return done[dev];
+}
+
 #define VIT_BY_DTYPE(KERN, G, B, ...)                                                             \
   do {                                                                                            \
     if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(KERN<BF16>, G, B, 0, (hipStream_t)s, __VA_ARGS__); \
     else hipLaunchKernelGGL(KERN<F16>, G, B, 0, (hipStream_t)s, __VA_ARGS__);                     \
   } while (0)
+
+// launch of an LDS-route kernel with `bytes` of dynamic LDS; false when the LDS limit could not be raised
+template <typename K, typename... A>
+static bool vl_launch(K kern, dim3 g, int threads, int bytes, pmi_stream_t s, A... args) {
+  if (!vl_allow_lds(kern, bytes)) return false;
+  hipLaunchKernelGGL(kern, g, dim3(threads), bytes, (hipStream_t)s, args...);
+  return true;
+}
+#define VIT_LDS_LAUNCH(KERN, G, B, BYTES, ...) \
+  (dtype == PMI_DT_BF16 ? vl_launch(KERN<BF16>, G, B, BYTES, s, __VA_ARGS__) : vl_launch(KERN<F16>, G, B, BYTES, s, __VA_ARGS__))
 
 extern "C" int pmi_vit_attn_fwd(const void* qkv, void* ws16, float* lse, void* out, int N, int T, int heads, float scale, int dtype,
                                 pmi_stream_t s) {
@@ -540,6 +904,13 @@ extern "C" int pmi_vit_attn_fwd(const void* qkv, void* ws16, float* lse, void* o
   const int Tp = (T + 31) / 32 * 32;
   const int64_t blk = (int64_t)N * heads * Tp * 64;
   u16* w = (u16*)ws16;   // Q, K, V, Qt, Kt, Vt
+  if (vit_lds_route(T, dtype)) {   // Q, K, V only: nothing reads the transposed parts on this route
+    const bool ok = VIT_LDS_LAUNCH(vit_attn_fwd_lds_kernel, dim3((Tp / 32 + VL_FWD_QT - 1) / VL_FWD_QT, N * heads), VL_FWD_QT * 64, 2 * Tp * 128, (const u16*)qkv,
+                                   w, w + blk, w + 2 * blk, (u16*)out, lse, T, Tp, heads, scale);
+    if (!ok) return PMI_ERR_LAUNCH;
+    PMI_CHECK_LAUNCH();
+    return PMI_OK;
+  }
   dim3 g(Tp / 32, N * heads);
   VIT_BY_DTYPE(vit_qkv_split_kernel, g, dim3(256), (const u16*)qkv, w, w + blk, w + 2 * blk, w + 3 * blk, w + 4 * blk, w + 5 * blk, T, Tp, heads);
   PMI_CHECK_LAUNCH();
@@ -555,6 +926,14 @@ extern "C" int pmi_vit_attn_bwd(const void* ws16, const float* lse, const void* 
   const int64_t blk = (int64_t)N * heads * Tp * 64;
   const u16* w = (const u16*)ws16;
   u16* wb = (u16*)ws16b;   // dO, dOt
+  if (vit_lds_route(T, dtype)) {   // ws16b and delta stay unwritten: dO and delta live in LDS
+    const int bytes = 4 * Tp * 128 + 2 * Tp * 4;
+    const bool ok = VIT_LDS_LAUNCH(vit_attn_bwd_lds_kernel, dim3(2, N * heads), VL_BWD_WAVES * 64, bytes, w, w + blk, w + 2 * blk, (const u16*)dout, (const u16*)o,
+                                   lse, (u16*)dqkv, T, Tp, heads, scale);
+    if (!ok) return PMI_ERR_LAUNCH;
+    PMI_CHECK_LAUNCH();
+    return PMI_OK;
+  }
   dim3 g(Tp / 32, N * heads);
   VIT_BY_DTYPE(vit_do_prep_kernel, g, dim3(256), (const u16*)dout, (const u16*)o, wb, wb + blk, delta, T, Tp, heads);
   PMI_CHECK_LAUNCH();

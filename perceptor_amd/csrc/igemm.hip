@@ -640,6 +640,7 @@ void pmi_gemm_wd_few_wgs(int v);            // gemm_wd.hip
 void pmi_conv3x3_wd_smallc(int v);          // conv3x3.hip
 void pmi_conv3x3_up_phase(int v);
 void pmi_conv3x3_skip_enable(int v);
+void pmi_vit_attn_lds(int v);               // attn.hip
 
 extern "C" int pmi_set_option(int key, int value) {
   if (key == 0) { const int old = g_allow_halo; g_allow_halo = value; return old; }
@@ -656,6 +657,7 @@ extern "C" int pmi_set_option(int key, int value) {
   if (key == 14) { pmi_attn_flash_kv_chunks(value); return 0; }
   if (key == 15) { pmi_conv3x3_up_phase(value); return 0; }
   if (key == 16) { pmi_conv3x3_skip_enable(value); return 0; }
+  if (key == 17) { pmi_vit_attn_lds(value); return 0; }
   return PMI_ERR_ARG;
 }
 
