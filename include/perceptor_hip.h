@@ -476,6 +476,20 @@ int pmi_style_level(const void* fa, const void* fb, const float* Ga, const float
 int pmi_gram_bwd(const void* fa, const void* fb, const void* S, void* T, const void* g_in, void* dF, int N, int HW, int C, float c_feat,
                  float c_gram, float gscale, int dtype, pmi_stream_t s);
 
+/* ---- LPIPS level (csrc/lpips.hip; perceptor/losses/lpips.py -> lpips 0.1 NetLinLayer over unit-normalised features), 16-bit NHWC features
+ * fa, fb [N][HW][C], dtype 0 / 1, fp32 arithmetic, no atomics (bit-identical from run to run).  C % 16 == 0, C <= 512, any HW >= 1; anything
+ * else is PMI_ERR_ARG without a launch.  eps = 1e-10.
+ * pmi_lpips_level: na = |fa|, nb = |fb| per pixel, s[n][p] = sum_c w[c] (fa_c / (na + eps) - fb_c / (nb + eps))^2, all fp32 [N][HW];
+ *   mean[n] = sum_p s[n][p] / HW.  w fp32 [C], NULL = all ones.  mean NULL: not computed and partial unused; else partial = 512 N floats.
+ * pmi_lpips_level_bwd: r [N][HW] fp32 = dL/ds; q_c = 2 r w_c (fa_c / (na + eps) - fb_c / (nb + eps));
+ *   dFa = (fa > 0) * ( gscale * ( q / (na + eps) - fa (fa . q) / (na (na + eps)^2) ) + g_in_a ), dFb the same with a and b swapped (q -> -q).
+ *   g_in_a / g_in_b nullable: the gradient arriving from deeper layers, already masked and scaled by gscale.  dFa / dFb nullable (not both):
+ *   one launch writes either side or both from one read of fa and fb.  At an all-zero pixel the gradient is 0 (autograd gives NaN there). */
+int pmi_lpips_level(const void* fa, const void* fb, const float* w, float* s_out, float* na, float* nb, float* mean, float* partial, int N,
+                    int HW, int C, int dtype, pmi_stream_t s);
+int pmi_lpips_level_bwd(const void* fa, const void* fb, const float* w, const float* na, const float* nb, const float* r, const void* g_in_a,
+                        const void* g_in_b, void* dFa, void* dFb, int N, int HW, int C, float gscale, int dtype, pmi_stream_t s);
+
 /* ---- Real-ESRGAN RRDBNet dense-block convolution (csrc/rrdb.hip), 16-bit NHWC, dtype 0 / 1, fp32 accumulation, forward only.
  * pmi_rdb_conv3x3: one 3x3 / pad 1 / stride 1 convolution over the channel prefix [0, Cin) of X (pixel pitch ldx elements) into the N-channel
  *   slice D (pixel pitch ldd), with everything the networks of perceptor/models/super_resolution/custom_rrdbnet_arch.py put around it:

@@ -178,6 +178,9 @@ _PROTOS = {
     "pmi_gram": ([_P, _P, _P, _I, _I, _I, _F, _I, _P],),
     "pmi_style_level": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],),
     "pmi_gram_bwd": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _I, _P],),
+    # LPIPS level and its adjoint (lpips.hip)
+    "pmi_lpips_level": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],),
+    "pmi_lpips_level_bwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P],),
     # Real-ESRGAN RRDBNet dense-block convolution (rrdb.hip)
     "pmi_rdb_conv3x3_eligible": ([_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I],),
     "pmi_rdb_conv3x3": ([_P, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _F, _F, _F, _I, _I, _I, _I, _I, _P],),

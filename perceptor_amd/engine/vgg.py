@@ -35,10 +35,11 @@ LOSS_LAST = 22                                                  # the loss path 
 GRAM_WEIGHT, LOSS_SCALE = 5e3, 0.001
 
 
-def layer_table(widths=VGG19_CONFIG[0]):
-    """The 37 modules of ``features``: ("conv", cin, cout) | ("relu",) | ("pool",), at torchvision's indices."""
+def layer_table(widths=VGG19_CONFIG[0], depths=DEPTHS):
+    """The modules of ``features`` (37 for VGG-19's depths): ("conv", cin, cout) | ("relu",) | ("pool",), at torchvision's indices.
+    depths: convolutions per group; (2, 2, 3, 3, 3) is VGG-16 (engine/lpips.py)."""
     out, cin = [], 3
-    for depth, w in zip(DEPTHS, widths):
+    for depth, w in zip(depths, widths):
         for _ in range(depth):
             out += [("conv", cin, w), ("relu",)]
             cin = w
@@ -46,34 +47,35 @@ def layer_table(widths=VGG19_CONFIG[0]):
     return out
 
 
-def conv_indices(widths=VGG19_CONFIG[0]):
-    return [i for i, l in enumerate(layer_table(widths)) if l[0] == "conv"]
+def conv_indices(widths=VGG19_CONFIG[0], depths=DEPTHS):
+    return [i for i, l in enumerate(layer_table(widths, depths)) if l[0] == "conv"]
 
 
-def vgg_state_dict_shapes(widths=VGG19_CONFIG[0]) -> Dict[str, Tuple[int, ...]]:
+def vgg_state_dict_shapes(widths=VGG19_CONFIG[0], depths=DEPTHS) -> Dict[str, Tuple[int, ...]]:
     S: Dict[str, Tuple[int, ...]] = {}
-    for i, l in enumerate(layer_table(widths)):
+    for i, l in enumerate(layer_table(widths, depths)):
         if l[0] == "conv":
             S[f"{i}.weight"] = (l[2], l[1], 3, 3)
             S[f"{i}.bias"] = (l[2],)
     return S
 
 
-def map_state_dict(sd, widths=VGG19_CONFIG[0]):
+def map_state_dict(sd, widths=VGG19_CONFIG[0], depths=DEPTHS):
     """torchvision's keys "{i}.weight" / "{i}.bias", with or without a "features." prefix; "classifier.*" is ignored."""
     out = {}
     for k, v in sd.items():
         if k.startswith("classifier."):
             continue
         out[k[len("features."):] if k.startswith("features.") else k] = v
-    want = vgg_state_dict_shapes(widths)
+    want = vgg_state_dict_shapes(widths, depths)
+    name = "VGG-19" if tuple(depths) == DEPTHS else f"VGG{tuple(depths)}"
     missing = [k for k in want if k not in out]
     extra = [k for k in out if k not in want]
     if missing or extra:
-        raise ValueError(f"VGG-19 state dict: missing {missing[:4]}, unexpected {extra[:4]}")
+        raise ValueError(f"{name} state dict: missing {missing[:4]}, unexpected {extra[:4]}")
     for k, shp in want.items():
         if tuple(out[k].shape) != shp:
-            raise ValueError(f"VGG-19 state dict: {k} has shape {tuple(out[k].shape)}, expected {shp}")
+            raise ValueError(f"{name} state dict: {k} has shape {tuple(out[k].shape)}, expected {shp}")
     return out
 
 
@@ -86,22 +88,25 @@ class _Conv:
 
 
 class VggEngine:
-    def __init__(self, cfg, state_dict, device, dtype="f16"):
+    def __init__(self, cfg, state_dict, device, dtype="f16", depths=DEPTHS):
+        """depths: convolutions per group (VGG-19's by default).  size None: no style-transfer size; images run at their own size only
+        (engine/lpips.py)."""
         widths, size = cfg
         widths = tuple(int(w) for w in widths)
-        if len(widths) != 5 or any(w <= 0 or w % 16 for w in widths) or size <= 0 or size % 32:
+        if len(widths) != 5 or any(w <= 0 or w % 16 for w in widths) or (size is not None and (size <= 0 or size % 32)):
             raise ValueError(f"unsupported VGG config {cfg}: five widths, each a multiple of 16, and size % 32 == 0 are required "
                              "(even maps at every pool)")
-        self.cfg, self.widths, self.size, self.device = (widths, int(size)), widths, int(size), torch.device(device)
+        size = None if size is None else int(size)
+        self.cfg, self.widths, self.size, self.device, self.depths = (widths, size), widths, size, torch.device(device), tuple(depths)
         if dtype not in ("f16", "bf16"):
             raise ValueError("the VGG tower runs in 'f16' or 'bf16'")
         self.dt = _hip.dtype_code(dtype)
         self.gscale = 1.0 if self.dt == _hip.DT_BF16 else 65536.0
         _hip.lib()
-        sd = map_state_dict(state_dict, widths)
-        self.layers = layer_table(widths)
+        sd = map_state_dict(state_dict, widths, self.depths)
+        self.layers = layer_table(widths, self.depths)
         self.convs = {i: _Conv(sd[f"{i}.weight"].detach().float().cpu(), sd[f"{i}.bias"].detach().float().cpu(), self.dt, self.device)
-                      for i in conv_indices(widths)}
+                      for i in conv_indices(widths, self.depths)}
         self.saved = None
 
     # ---- pieces ---------------------------------------------------------------------------------------

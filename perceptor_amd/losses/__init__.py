@@ -5,5 +5,6 @@ from .aesthetic import AestheticVisualAssessment, SimulacraAesthetic
 from .pixel import Resize, Smoothness
 from .spherical_distance import SphericalDistance
 from .shared_tower import tower_loss_and_grad
+from .lpips import LPIPS
 from .style_transfer import StyleTransfer
 from .super_resolution import SuperResolution
