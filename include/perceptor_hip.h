@@ -406,6 +406,16 @@ int pmi_unpatchify(const float* dcol, const float* stdv, float* dimg, int N, int
 int pmi_act_fwd(const void* in, void* out, int64_t n, int act, int dtype, pmi_stream_t s);   /* QuickGELU / GELU (ruclip/model.py:20-23) */
 int pmi_l2norm_rows(const float* x, float* y, int M, int D, float scale, pmi_stream_t s);    /* scale * F.normalize(x): models/open_clip.py:120-121, cc12m_1.py:294 */
 int pmi_vit_assemble(const float* emb, const float* cls, const float* pos, float* x, int N, int T, int D, int r0, pmi_stream_t s);
+/* GLIDE CLIP image stem (perceptor/models/glide_clip/encoders.py), one launch per direction, fp32 on the vector ALU (glide.hip).
+ * fwd: a = (255 img - mean_c) / std_c; x0[n][1+p] = w a_p + pos[1+p], x0[n][0] = w_t[clamp(ts[n], 0, n_timestep-1)] + pos[0];
+ *      x = LayerNorm(x0) * gamma + beta; mean_rstd[2][N*T] as pmi_layernorm_bwd reads it.  w is [W][3 P P], k = c P^2 + py P + px.
+ * bwd: dimg = mul * 255 / std_c * sum_j w[j][k] * LN'(g)[j] over the patch rows (token 0's row is dropped); every pixel is stored once.
+ * P must be 4, W a multiple of 64 up to 2048, R a multiple of P; anything else returns PMI_ERR_ARG before a launch. */
+int pmi_glide_embed_fwd(const float* img, const float* mean, const float* stdv, const float* w, const int64_t* ts, const float* w_t,
+                        const float* pos, const float* gamma, const float* beta, float* x0, float* x, float* mean_rstd,
+                        int N, int R, int P, int W, int n_timestep, float eps, pmi_stream_t s);
+int pmi_glide_embed_bwd(const float* g, const float* x0, const float* gamma, const float* mean_rstd, const float* w, const float* stdv,
+                        float* dimg, int N, int R, int P, int W, float mul, pmi_stream_t s);
 /* losses/clip/clip.py:89-99 (+ F.normalize of models/open_clip.py:120-121): loss = mult * sum_{n,k} w_k 2 asin(|e_n-t_k|/2)^2 / (n_total*K);
  * demb = gscale * dloss/demb (emb un-normalised).  n_total = global batch (>= N) so a sharded batch keeps the global mean. */
 int pmi_spherical_loss(const float* emb, const float* tgt, const float* wts, float* loss, float* demb, int N, int K, int D,

@@ -159,6 +159,9 @@ _PROTOS = {
     "pmi_act_fwd": ([_P, _P, _L, _I, _I, _P],),
     "pmi_l2norm_rows": ([_P, _P, _I, _I, _F, _P],),
     "pmi_vit_assemble": ([_P, _P, _P, _P, _I, _I, _I, _I, _P],),
+    # GLIDE CLIP patch stem, forward and adjoint (glide.hip)
+    "pmi_glide_embed_fwd": ([_P] * 12 + [_I, _I, _I, _I, _I, _F, _P],),
+    "pmi_glide_embed_bwd": ([_P] * 7 + [_I, _I, _I, _I, _F, _P],),
     "pmi_spherical_loss": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P],),
     # CLIP ResNet towers (resnet.hip)
     "pmi_rn_stage_input": ([_P, _P, _P, _P, _I, _I, _I, _I, _P],),

@@ -12,7 +12,7 @@ The residual stream is fp32 in HBM; GEMM operands are 16-bit on the MFMA (fp32 a
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -120,11 +120,13 @@ class TextEngine:
         return y16, y32
 
     @torch.no_grad()
-    def forward(self, ids: torch.Tensor):
+    def forward(self, ids: torch.Tensor, lengths: Optional[torch.Tensor] = None):
         """ids [N, T] int64 (T <= context) -> (hidden [N, T, width] fp32 after ln_final, pooled [N, out_dim] fp32 or None).
 
         pooled = hidden[n, argmax(ids[n])] @ text_projection: the EOT token has the largest id of the CLIP vocabulary
-        (OpenAI-CLIP ``x[arange, text.argmax(-1)]``; ruclip/model.py:224-227 selects the same row by eos_id)."""
+        (OpenAI-CLIP ``x[arange, text.argmax(-1)]``; ruclip/model.py:224-227 selects the same row by eos_id).
+        lengths (int64 [N], 1..T): pool row lengths - 1 instead (GLIDE CLIP, glide_clip/encoders.py:334-342, which gathers the row and
+        then applies the LayerNorm: the same values row for row, LayerNorm acts on each row alone)."""
         ctx, vocab, width, layers, heads, out = self.cfg
         if ids.ndim != 2 or ids.dtype != torch.int64:
             raise ValueError("ids must be an int64 tensor of shape [N, T]")
@@ -133,6 +135,11 @@ class TextEngine:
             raise ValueError(f"sequence length {t} exceeds the context length {ctx}")
         if int(ids.min()) < 0 or int(ids.max()) >= vocab:
             raise ValueError("token id out of range")
+        if lengths is not None:
+            if lengths.ndim != 1 or lengths.shape[0] != n or lengths.dtype != torch.int64:
+                raise ValueError("lengths must be an int64 tensor of shape [N]")
+            if int(lengths.min()) < 1 or int(lengths.max()) > t:
+                raise ValueError("lengths out of range")
         dev, dt = self.device, self.dt
         ids = ids.to(dev).contiguous()
         m = n * t
@@ -150,7 +157,7 @@ class TextEngine:
         _, hidden = self._ln(x, self.ln_final, m, width, want16=False, want32=True)
         pooled = None
         if self.proj is not None:
-            rows = ids.argmax(dim=1) + torch.arange(n, device=dev) * t
+            rows = (ids.argmax(dim=1) if lengths is None else lengths.to(dev) - 1) + torch.arange(n, device=dev) * t
             eot = torch.empty((n, width), dtype=torch.float32, device=dev)
             call("pmi_gather_rows", ptr(hidden), ptr(rows), ptr(eot), n, width, width, m)
             e16 = torch.empty((n, width), dtype=_hip.TORCH_DTYPE[dt], device=dev)

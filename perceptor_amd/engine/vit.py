@@ -176,6 +176,40 @@ class VitEngine:
             return g32, g16
         return self._ln_bwd(dy, d, x, gb, mr, gres, m, d)
 
+    # ---- the stem, both directions: the two seams a tower with another stem overrides (engine/glide.py) --------------
+    def _embed(self, images):
+        """images -> (x0 [N, T, width] fp32 before ln_pre, kept for the backward; x [N*T, width] fp32, the residual stream the first
+        block reads; mr_pre, ln_pre's mean / rstd)."""
+        res, patch, width, layers, heads, out = self.cfg
+        dt, dev = self.dt, self.device
+        n = images.shape[0]
+        g = res // patch
+        t = g * g + 1
+        resized = _resize(images, (res, res))
+        col = torch.empty((n * g * g, self.kp), dtype=_hip.TORCH_DTYPE[dt], device=dev)
+        call("pmi_patchify", ptr(resized), ptr(self.mean), ptr(self.std), ptr(col), n, res, patch, self.kp, 0, dt)
+        pe = ops.igemm(col, self.conv1.fwd, out_f32=True)
+        x0 = torch.empty((n, t, width), dtype=torch.float32, device=dev)
+        call("pmi_vit_assemble", ptr(pe), ptr(self.cls), ptr(self.pos), ptr(x0), n, t, width, 0)
+        _, x, mr_pre = self._ln(x0, width, self.ln_pre, n * t, width, want16=False, want32=True)
+        return x0, x, mr_pre
+
+    def _embed_backward(self, g32, sv, record=None):
+        """g32: the fp32 gradient at the first block's input (times gscale) -> dL/d(images), fp32 NCHW at the size forward() was given."""
+        res, patch, width, layers, heads, out = self.cfg
+        dt, dev = self.dt, self.device
+        n = sv["n"]
+        t = (res // patch) ** 2 + 1
+        _, g0 = self._ln_bwd(g32, width, sv["x0"], self.ln_pre, sv["mr_pre"], None, n * t, width, want32=False)
+        dcol = torch.empty((n * (t - 1), self.kp), dtype=torch.float32, device=dev)
+        ops.bgemm(g0, self.conv1.bwd.w, dcol, M=t - 1, N=self.kp, K=width, lda=width, ldb=width, ldd=self.kp, batch=n, batch_inner=1,
+                  sA=(t * width, 0), sB=(0, 0), sD=((t - 1) * self.kp, 0), dt=dt, a_off=width)
+        dres = torch.empty((n, 3, res, res), dtype=torch.float32, device=dev)
+        call("pmi_unpatchify", ptr(dcol), ptr(self.std), ptr(dres), n, res, patch, self.kp, 1.0 / self.gscale)
+        if record is not None:
+            record.update(g0=g0, dcol=dcol)
+        return _resize_backward(dres, sv["in_hw"])
+
     # ---- forward --------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, images: torch.Tensor, save: bool = False, features: bool = False):
@@ -191,13 +225,7 @@ class VitEngine:
         t = g * g + 1
         m = n * t
         d = width // heads
-        resized = _resize(images, (res, res))
-        col = torch.empty((n * g * g, self.kp), dtype=tdt, device=dev)
-        call("pmi_patchify", ptr(resized), ptr(self.mean), ptr(self.std), ptr(col), n, res, patch, self.kp, 0, dt)
-        pe = ops.igemm(col, self.conv1.fwd, out_f32=True)
-        x0 = torch.empty((n, t, width), dtype=torch.float32, device=dev)
-        call("pmi_vit_assemble", ptr(pe), ptr(self.cls), ptr(self.pos), ptr(x0), n, t, width, 0)
-        _, x, mr_pre = self._ln(x0, width, self.ln_pre, m, width, want16=False, want32=True)
+        x0, x, mr_pre = self._embed(images)
         sv = dict(in_hw=tuple(images.shape[2:]), n=n, x0=x0, mr_pre=mr_pre, layers=[]) if save else None
         fuse = width % 256 == 0 and width <= 2048            # split-K reduce of the MLP's last GEMM + the next block's LayerNorm in one pass
         nxt = None                                           # (h, mr1) of this block when the previous block's tail already produced them
@@ -285,13 +313,6 @@ class VitEngine:
             if record is not None:
                 record["gm32"].append(gm32)
                 record["g32"].append(g32)
-        _, g0 = self._ln_bwd(g32, width, sv["x0"], self.ln_pre, sv["mr_pre"], None, m, width, want32=False)
-        dcol = torch.empty((n * (t - 1), self.kp), dtype=torch.float32, device=dev)
-        ops.bgemm(g0, self.conv1.bwd.w, dcol, M=t - 1, N=self.kp, K=width, lda=width, ldb=width, ldd=self.kp, batch=n, batch_inner=1,
-                  sA=(t * width, 0), sB=(0, 0), sD=((t - 1) * self.kp, 0), dt=dt, a_off=width)
-        dres = torch.empty((n, 3, res, res), dtype=torch.float32, device=dev)
-        call("pmi_unpatchify", ptr(dcol), ptr(self.std), ptr(dres), n, res, patch, self.kp, 1.0 / self.gscale)
-        if record is not None:
-            record.update(g0=g0, dcol=dcol)
+        dimg = self._embed_backward(g32, sv, record)
         self.saved = None
-        return _resize_backward(dres, sv["in_hw"])
+        return dimg

@@ -8,3 +8,4 @@ from .simulacra_aesthetic import SimulacraAesthetic
 from .vgg import VGG19
 from .super_resolution import SuperResolution
 from .monster_diffusion import MonsterDiffusion
+from .glide_clip import GlideCLIP
