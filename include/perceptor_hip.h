@@ -607,6 +607,37 @@ int pmi_jpeg_decode_bwd(const float* y, const float* cb, const float* cr, float 
                         float* d_cr, int N, int H, int W, pmi_stream_t s);
 int pmi_jpeg_encode(const float* images, float factor, int round_mode, float* y, float* cb, float* cr, int N, int H, int W, pmi_stream_t s);
 
+/* ---- OWL-ViT detection heads on the ViT tower's last hidden state (owlvit.hip); fp32 unless stated, no float atomics: two runs are bit-equal ----
+ * pmi_owl_merge_ln_fwd: x [N][T][W] (the last hidden state).  y = LayerNorm(x; g1, b1) on all T rows (post_layernorm), m[p] = y[p + 1] * y[0]
+ *   (the class-token merge), feats = LayerNorm(m; g2, b2) for the P = T - 1 patch rows, written as fp32 feats32 [N P][W] and as the 16-bit
+ *   GEMM operand feats16 (dtype f16 / bf16).  mean_rstd1 [2][N T] and mean_rstd2 [2][N P] receive (mean | rstd) of the two norms.  One launch.
+ *   W % 4 == 0, W <= 2048, T >= 2, pointers 16-byte aligned.
+ * pmi_owl_merge_ln_bwd: the exact adjoint: dfeats [N P][W] -> dx [N][T][W], every row written.  The class row's gradient is the sum over an
+ *   image's patch rows: pmi_owl_merge_bwd_blocks(T) partial rows per image (partials: [N][blocks][W] floats of workspace) summed in a fixed
+ *   order by a second launch.  Two launches.
+ * pmi_owl_class_logits_fwd: g [M][ldg] = the packed class-head GEMM's fp32 output (columns 0..D-1 dense0, D logit_shift, D + 1 logit_scale, bias
+ *   included; the rest padding), q [Q][D] the prepared queries.  class_embeds [M][D] = e / (|e| + 1e-6); logits [M][Q] =
+ *   (class_embeds . q + shift) * (elu(scale) + 1).  D <= 1024, Q D <= 12288 (the query block is staged in LDS once per workgroup).
+ * pmi_owl_class_logits_bwd: dlogits [M][Q] -> dg [M][ldg] 16-bit (dtype), the gradient at g and the operand of the transposed-weight GEMM:
+ *   D columns through the normalisation, the shift column, the scale column through ELU', zeros in the padding.
+ * pmi_owl_topk_loss: logits [N][P][Q], weights [Q].  Per (n, q): log-softmax over the P tokens, S = the k_eff = min(k, P) largest (ties: the
+ *   lower index); partials [N Q] receives -0.01 w_q / (N k_eff) sum_{p in S} logsoftmax_p (the loss is their sum) and
+ *   dlogits[n][p][q] = mul * -0.01 w_q / (N k_eff) ([p in S] - k_eff softmax_p).  One workgroup per (n, q); P <= 16256 (64 KB of LDS), k <= 64.
+ * pmi_owl_box_out: h [M][ldh] 16-bit (the box head after dense1 + GELU), w2 [4][W], b2 [4], box_bias [P][4] ->
+ *   boxes [M][4] = sigmoid(h w2^T + b2 + box_bias[row % P]).  W % 8 == 0. */
+int pmi_owl_merge_ln_fwd(const float* x, const float* g1, const float* b1, const float* g2, const float* b2, float* feats32, void* feats16,
+                         float* mean_rstd1, float* mean_rstd2, int N, int T, int W, float eps, int dtype, pmi_stream_t s);
+int pmi_owl_merge_bwd_blocks(int T);
+int pmi_owl_merge_ln_bwd(const float* dfeats, const float* x, const float* g1, const float* b1, const float* g2, const float* mean_rstd1,
+                         const float* mean_rstd2, float* dx, float* partials, int N, int T, int W, pmi_stream_t s);
+int pmi_owl_class_logits_fwd(const float* g, int ldg, const float* q, float* logits, float* class_embeds, int64_t M, int D, int Q, pmi_stream_t s);
+int pmi_owl_class_logits_bwd(const float* dlogits, const float* g, int ldg, const float* q, void* dg, int64_t M, int D, int Q, int dtype,
+                             pmi_stream_t s);
+int pmi_owl_topk_loss(const float* logits, const float* weights, float* dlogits, float* partials, int N, int P, int Q, int k, float mul,
+                      pmi_stream_t s);
+int pmi_owl_box_out(const void* h, int ldh, const float* w2, const float* b2, const float* box_bias, float* boxes, int64_t M, int P, int W,
+                    int dtype, pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,14 @@ _PROTOS = {
     # GLIDE CLIP patch stem, forward and adjoint (glide.hip)
     "pmi_glide_embed_fwd": ([_P] * 12 + [_I, _I, _I, _I, _I, _F, _P],),
     "pmi_glide_embed_bwd": ([_P] * 7 + [_I, _I, _I, _I, _F, _P],),
+    # OWL-ViT detection heads (owlvit.hip)
+    "pmi_owl_merge_ln_fwd": ([_P] * 9 + [_I, _I, _I, _F, _I, _P],),
+    "pmi_owl_merge_bwd_blocks": ([_I],),
+    "pmi_owl_merge_ln_bwd": ([_P] * 9 + [_I, _I, _I, _P],),
+    "pmi_owl_class_logits_fwd": ([_P, _I, _P, _P, _P, _L, _I, _I, _P],),
+    "pmi_owl_class_logits_bwd": ([_P, _P, _I, _P, _P, _L, _I, _I, _I, _P],),
+    "pmi_owl_topk_loss": ([_P, _P, _P, _P, _I, _I, _I, _I, _F, _P],),
+    "pmi_owl_box_out": ([_P, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P],),
     "pmi_spherical_loss": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P],),
     # CLIP ResNet towers (resnet.hip)
     "pmi_rn_stage_input": ([_P, _P, _P, _P, _I, _I, _I, _I, _P],),

@@ -72,6 +72,13 @@ def from_hf_text_state_dict(hf: Dict[str, torch.Tensor]) -> Dict[str, torch.Tens
     return out
 
 
+def from_owlvit_text_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """transformers' OwlViTForObjectDetection keys (``owlvit.text_model.*``, ``owlvit.text_projection.weight``) -> the OpenAI-CLIP names this
+    engine packs."""
+    hf = {k[len("owlvit."):]: v for k, v in sd.items() if k.startswith("owlvit.text_model.") or k == "owlvit.text_projection.weight"}
+    return from_hf_text_state_dict(hf)
+
+
 def hf_text_state_dict_shapes(cfg, projection: bool = True) -> Dict[str, Tuple[int, ...]]:
     """The text tower under transformers' key names (CLIPTextModel[WithProjection])."""
     ctx, vocab, width, layers, heads, out = cfg

@@ -75,6 +75,14 @@ def from_hf_vision_state_dict(hf: Dict[str, torch.Tensor]) -> Dict[str, torch.Te
     return out
 
 
+def from_owlvit_vision_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """transformers' OwlViTForObjectDetection keys (``owlvit.vision_model.*`` with ``pre_layernorm`` spelled out, ``owlvit.visual_projection.weight``)
+    -> the OpenAI-CLIP names this engine packs."""
+    hf = {k[len("owlvit."):].replace("pre_layernorm", "pre_layrnorm"): v for k, v in sd.items()
+          if k.startswith("owlvit.vision_model.") or k == "owlvit.visual_projection.weight"}
+    return from_hf_vision_state_dict(hf)
+
+
 def hf_vision_state_dict_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
     """The same tower under transformers' key names (what ``TransformersOpenAICLIP.state_dict()`` holds)."""
     res, patch, width, layers, heads, out = cfg
@@ -293,6 +301,33 @@ class VitEngine:
         g32 = torch.zeros((m, width), dtype=torch.float32, device=dev)
         g16 = torch.zeros((m, width), dtype=tdt, device=dev)
         self._ln_bwd(dy_post, dy_post.shape[1], sv["x_final"], self.ln_post, sv["mr_post"], None, n, width, row_stride=t, g32=g32, g16=g16)
+        return self._backward_blocks(g32, g16, sv, record)
+
+    @torch.no_grad()
+    def backward_tokens(self, d_hidden: torch.Tensor, record: Optional[dict] = None) -> torch.Tensor:
+        """d_hidden: dL/d(last hidden state, BEFORE ln_post) * self.gscale, fp32 [N, T, width], a gradient on every token (what a loss on
+        dense features hands back: engine/owlvit.py)  ->  dL/d(images), fp32 NCHW, exactly as backward().  record: as backward()."""
+        sv = self.saved
+        if sv is None:
+            raise RuntimeError("call forward(images, save=True) before backward_tokens()")
+        res, patch, width, layers, heads, out = self.cfg
+        t = (res // patch) ** 2 + 1
+        m = sv["n"] * t
+        if d_hidden.dtype != torch.float32 or tuple(d_hidden.shape) != (sv["n"], t, width):
+            raise ValueError(f"d_hidden must be fp32 [{sv['n']}, {t}, {width}]")
+        g32 = d_hidden.contiguous().view(m, width)
+        g16 = torch.empty((m, width), dtype=_hip.TORCH_DTYPE[self.dt], device=self.device)
+        call("pmi_cast_f32_to_16", ptr(g32), ptr(g16), m * width, ACT_NONE, self.dt)
+        return self._backward_blocks(g32, g16, sv, record)
+
+    def _backward_blocks(self, g32, g16, sv, record):
+        """The walk both entries share: (g32, g16) = the gradient at the last block's output (times gscale), fp32 and as the 16-bit GEMM
+        operand -> through the blocks, last first, and the stem, to the images."""
+        res, patch, width, layers, heads, out = self.cfg
+        dt = self.dt
+        n = sv["n"]
+        t = (res // patch) ** 2 + 1
+        m = n * t
         if record is not None:
             record.update(g32=[g32], gm32=[])
         for blk, L in zip(reversed(self.blocks), reversed(sv["layers"])):

@@ -8,3 +8,4 @@ from .shared_tower import tower_loss_and_grad
 from .lpips import LPIPS
 from .style_transfer import StyleTransfer
 from .super_resolution import SuperResolution
+from .owlvit import OWLViT

@@ -9,3 +9,4 @@ from .vgg import VGG19
 from .super_resolution import SuperResolution
 from .monster_diffusion import MonsterDiffusion
 from .glide_clip import GlideCLIP
+from .owlvit import OWLViT, OWLViTEncodings, OWLViTPredictions
