@@ -638,6 +638,51 @@ int pmi_owl_topk_loss(const float* logits, const float* weights, float* dlogits,
 int pmi_owl_box_out(const void* h, int ldh, const float* w2, const float* b2, const float* box_bias, float* boxes, int64_t M, int P, int W,
                     int dtype, pmi_stream_t s);
 
+/* ---- DeepImagePrior: a skip network trained through its WEIGHTS (dip.hip, the 8-tap resamplers in fir.hip) ----
+ * Tensors are NHWC 16-bit (dtype = f16 / bf16), C a multiple of 4, pointers 8-byte aligned.  "ring r" (0 or 1): the tensor is
+ * [N, H + 2r, W + 2r, ld] and its interior is the H x W map.  Parameters, statistics and parameter gradients are fp32.  No float atomics.
+ * pmi_dip_pack_w: w [Cout][Cin][taps] fp32 -> fwd [n_p][taps][cin_p] (pmi_igemm's B, zero padded) and, unless NULL, dxp [rows_p][taps][cout_p] =
+ *   w transposed with the taps reversed (the input-gradient convolution's B).  Runs every forward: no packing outlives a weight update.
+ * pmi_dip_wgrad: dW [Cout][Cin][taps] (PyTorch's layout) = alpha sum_{n,y,x} dY[n,y,x,co] X[n,y+ky,x+kx,ci], db [Cout] = alpha sum dY (NULL: skipped).
+ *   taps 9: X has ring 1 (the padded input the forward convolved); taps 1: X's interior pixel.  Cout > 4: MFMA 32x32x16 on pixel-major LDS tiles
+ *   read with ds_read_b64_tr_b16 (rows 16-byte aligned, ld % 8 == 0, ld >= the channel count rounded up to 8); Cout <= 4: a plain reduction.
+ *   slabs: splits * (Cout Cin taps + Cout) floats, splits = pmi_dip_wgrad_splits(N H W, Cout, Cin, taps); a fixed-order reduce sums them.
+ * pmi_dip_bn_stats: mean [C], rstd [C] = 1 / sqrt(biased var + eps) over N H W (partial sums, then a centred second pass); running_mean /
+ *   running_var (NULL: untouched) move by `momentum` toward the mean and the UNBIASED variance.  part: pmi_dip_bn_blocks(N H W) * C floats.
+ * pmi_dip_bn_apply: y = act(a x + b), a = gamma rstd, b = beta - mean a; act 0 none, 1 LeakyReLU(0.2).  y has pitch ldy (a channel slice of a wider
+ *   tensor through the pointer) and ring y_ring, which is filled by reflection.
+ * pmi_dip_bn_bwd: sums [2][C] = (sum dy', sum dy' xhat), dy' = dy act'(a x + b); dbeta = alpha sums[0], dgamma = alpha sums[1] (NULL: skipped);
+ *   dx = a (dy' - sums[0] / P - xhat sums[1] / P) into the interior of a tensor with ring dx_ring (the ring is the caller's).  dy has no ring.
+ *   part: 2 * pmi_dip_bn_blocks(N H W) * C floats.
+ * pmi_dip_reflect_pad: [N, H, W, C] -> [N, H + 2, W + 2, C];  pmi_dip_pad_fold: its adjoint (+ add, NULL or [N, H, W, C]).
+ * pmi_dip_head_fwd: out NCHW fp32 = sigmoid?(cm^T (w x + b)): w [Cout][Cin], Cout <= 4, Cin % 8 == 0 and <= 512; cm: NULL or the row-major 3 x 3
+ *   matrix of einsum("nchw,cd->ndhw").  pmi_dip_head_bwd: dz [N HW][8] 16-bit = scale cm (dout sigmoid'(out)), channels Cout .. 7 zero.
+ * pmi_fir8_*: the 8-tap cubic resamplers (reflect pad 3 resp. 2) and their exact adjoints in gather form; H, W are the FORWARD input's size.
+ *   down2: x ring x_ring -> [N, H/2, W/2, C], H, W even and >= 4; up2: -> [N, 2H, 2W, C], H, W >= 3; down2_bwd writes a ring-dx_ring tensor. */
+int pmi_dip_pack_w(const float* w, void* fwd, void* dxp, int Cout, int Cin, int taps, int n_p, int cin_p, int rows_p, int cout_p, int dtype,
+                   pmi_stream_t s);
+int pmi_dip_wgrad_splits(int64_t P, int Cout, int Cin, int taps);
+int pmi_dip_wgrad(const void* dy, int ldy, int dy_ring, const void* x, int ldx, int x_ring, float* slabs, float* dW, float* db, int N, int H,
+                  int W, int Cout, int Cin, int taps, int splits, float alpha, int dtype, pmi_stream_t s);
+int pmi_dip_bn_blocks(int64_t P);
+int pmi_dip_bn_stats(const void* x, int ldx, int x_ring, float* part, float* mean, float* rstd, float* running_mean, float* running_var, int N,
+                     int H, int W, int C, float momentum, float eps, int dtype, pmi_stream_t s);
+int pmi_dip_bn_apply(const void* x, int ldx, int x_ring, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y,
+                     int ldy, int y_ring, int N, int H, int W, int C, int act, int dtype, pmi_stream_t s);
+int pmi_dip_bn_bwd(const void* x, int ldx, int x_ring, const void* dy, int lddy, const float* mean, const float* rstd, const float* gamma,
+                   const float* beta, float* part, float* sums, float* dgamma, float* dbeta, void* dx, int lddx, int dx_ring, int N, int H, int W,
+                   int C, int act, float alpha, int dtype, pmi_stream_t s);
+int pmi_dip_reflect_pad(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_dip_pad_fold(const void* gp, const void* add, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_dip_head_fwd(const void* x, const float* w, const float* bias, const float* cm, float* out, int N, int HW, int Cin, int Cout, int sigmoid,
+                     int dtype, pmi_stream_t s);
+int pmi_dip_head_bwd(const float* dout, const float* out, const float* cm, void* dz, int N, int HW, int Cout, int sigmoid, float scale, int dtype,
+                     pmi_stream_t s);
+int pmi_fir8_down2(const void* x, int x_ring, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_fir8_up2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_fir8_down2_bwd(const void* dy, void* dx, int dx_ring, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_fir8_up2_bwd(const void* dy, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

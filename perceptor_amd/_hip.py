@@ -217,6 +217,22 @@ _PROTOS = {
     "pmi_jpeg_decode": ([_P, _P, _P, _F, _P, _I, _I, _I, _P],),
     "pmi_jpeg_decode_bwd": ([_P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _P],),
     "pmi_jpeg_encode": ([_P, _F, _I, _P, _P, _P, _I, _I, _I, _P],),
+    # DeepImagePrior: weight gradients, training-mode BatchNorm, reflect pad / fold, output head (dip.hip), 8-tap resamplers (fir.hip)
+    "pmi_dip_pack_w": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],),
+    "pmi_dip_wgrad_splits": ([_L, _I, _I, _I],),
+    "pmi_dip_wgrad": ([_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P],),
+    "pmi_dip_bn_blocks": ([_L],),
+    "pmi_dip_bn_stats": ([_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _I, _P],),
+    "pmi_dip_bn_apply": ([_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],),
+    "pmi_dip_bn_bwd": ([_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P],),
+    "pmi_dip_reflect_pad": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_dip_pad_fold": ([_P, _P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_dip_head_fwd": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],),
+    "pmi_dip_head_bwd": ([_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],),
+    "pmi_fir8_down2": ([_P, _I, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_fir8_up2": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_fir8_down2_bwd": ([_P, _P, _I, _I, _I, _I, _I, _I, _P],),
+    "pmi_fir8_up2_bwd": ([_P, _P, _I, _I, _I, _I, _I, _P],),
 }
 
 

@@ -182,3 +182,177 @@ extern "C" int pmi_fir_down2_bwd(const void* dy, void* dx, int N, int H, int W, 
 extern "C" int pmi_fir_up2_bwd(const void* dy, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
   return fir_bwd<true>(dy, dx, N, H, W, C, dtype, s);
 }
+
+// ---- the 8-tap "cubic" resamplers of the DeepImagePrior skip network (deep_image_prior/updown.py) ----------------------------------------------
+//   pmi_fir8_down2   reflect-pad 3, depthwise 8x8 kernel k k^T, k = [-3, -9, 29, 111, 111, 29, -9, -3] / 256, stride 2   [N, H, W, C] -> [N, H/2, W/2, C]
+//   pmi_fir8_up2     reflect-pad 2, conv_transpose2d with (2k)(2k)^T, stride 2, padding 7                               [N, H, W, C] -> [N, 2H, 2W, C]
+// Per axis: down[o] = sum_t k[t] x[refl(2o - 3 + t)];  up[2m] = sum_d 2k[7 - 2d] x[refl(m + d - 2)],  up[2m + 1] = sum_d 2k[6 - 2d] x[refl(m + d - 1)].
+// The long-kernel siblings of the 4-tap kernels above: reflection as index arithmetic, one thread per output pixel and 4 channels (C a multiple
+// of 4: the network's 4-channel skip shares them), fp32 sums, one rounding at the store.  The source of down2 and the destination of down2_bwd
+// may carry a one-pixel ring ([N, H + 2, W + 2, C], interior H x W): the 3x3 convolutions beside them run on ringed tensors.
+// Adjoints in gather form: an input index i is read through the padded positions u = i, u = -i (1 <= i <= pad) and u = 2(n - 1) - i (when
+// that lies in n .. n + pad - 1); each u collects the outputs whose taps reach it.  No atomics.
+namespace {
+
+__constant__ float k8[8] = {-0.01171875f, -0.03515625f, 0.11328125f, 0.43359375f, 0.43359375f, 0.11328125f, -0.03515625f, -0.01171875f};
+
+__device__ __forceinline__ int refl_n(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
+__device__ __forceinline__ int64_t ring_off(int n, int y, int x, int H, int W, int r, int C) {
+  return (((int64_t)n * (H + 2 * r) + (y + r)) * (W + 2 * r) + (x + r)) * C;
+}
+template <typename T>
+__device__ __forceinline__ void ld4(const u16* p, float* f) {
+  const uint2 v = *(const uint2*)p;
+  f[0] = T::to_f((u16)(v.x & 0xffff)); f[1] = T::to_f((u16)(v.x >> 16));
+  f[2] = T::to_f((u16)(v.y & 0xffff)); f[3] = T::to_f((u16)(v.y >> 16));
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fir8_down2_kernel(const u16* __restrict__ x, int xr, u16* __restrict__ y, int N, int H, int W, int C) {
+  const int G = C >> 2, Ho = H / 2, Wo = W / 2;
+  const int64_t total = (int64_t)N * Ho * Wo * G;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int g = (int)(i % G);
+    const int64_t pix = i / G;
+    const int n = (int)(pix / ((int64_t)Ho * Wo)), rem = (int)(pix - (int64_t)n * Ho * Wo), oy = rem / Wo, ox = rem - oy * Wo;
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int r = 0; r < 8; ++r) {
+      const int iy = refl_n(2 * oy - 3 + r, H);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        float f[4];
+        ld4<T>(x + ring_off(n, iy, refl_n(2 * ox - 3 + t, W), H, W, xr, C) + 4 * g, f);
+        const float wgt = k8[r] * k8[t];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = fmaf(wgt, f[e], o[e]);
+      }
+    }
+    *(uint2*)(y + pix * C + 4 * g) = pack4<T>(o[0], o[1], o[2], o[3]);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fir8_up2_kernel(const u16* __restrict__ x, u16* __restrict__ y, int N, int H, int W, int C) {
+  const int G = C >> 2, Ho = 2 * H, Wo = 2 * W;
+  const int64_t total = (int64_t)N * Ho * Wo * G;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int g = (int)(i % G);
+    const int64_t pix = i / G;
+    const int n = (int)(pix / ((int64_t)Ho * Wo)), rem = (int)(pix - (int64_t)n * Ho * Wo), oy = rem / Wo, ox = rem - oy * Wo;
+    const int py = oy & 1, px = ox & 1, my = oy >> 1, mx = ox >> 1;
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int iy = refl_n(my + a - 2 + py, H);
+      const float wy = 2.f * k8[7 - py - 2 * a];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        float f[4];
+        ld4<T>(x + (((int64_t)n * H + iy) * W + refl_n(mx + b - 2 + px, W)) * C + 4 * g, f);
+        const float wgt = wy * (2.f * k8[7 - px - 2 * b]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = fmaf(wgt, f[e], o[e]);
+      }
+    }
+    *(uint2*)(y + pix * C + 4 * g) = pack4<T>(o[0], o[1], o[2], o[3]);
+  }
+}
+
+// (index, weight) of every output that reads input i of an axis of n samples; at most 12 (down) or 24 (up) entries
+template <bool UP>
+__device__ __forceinline__ int fir8_bwd_taps(int i, int n, int* idx, float* w) {
+  constexpr int PAD = UP ? 2 : 3;
+  const int hi = 2 * (n - 1) - i;
+  const int u[3] = {i, -i, hi};
+  const bool v[3] = {true, i >= 1 && i <= PAD, hi >= n && hi <= n + PAD - 1};
+  int cnt = 0;
+  for (int c = 0; c < 3; ++c) {
+    if (!v[c]) continue;
+    if (UP) {
+      for (int d = 0; d < 4; ++d) {
+        const int m0 = u[c] - d + 2, m1 = u[c] - d + 1;
+        if (m0 >= 0 && m0 < n) { idx[cnt] = 2 * m0; w[cnt] = 2.f * k8[7 - 2 * d]; ++cnt; }
+        if (m1 >= 0 && m1 < n) { idx[cnt] = 2 * m1 + 1; w[cnt] = 2.f * k8[6 - 2 * d]; ++cnt; }
+      }
+    } else {
+      for (int t = 0; t < 8; ++t) {
+        const int q = u[c] + 3 - t;
+        if (q < 0 || (q & 1) || (q >> 1) >= n / 2) continue;
+        idx[cnt] = q >> 1; w[cnt] = k8[t]; ++cnt;
+      }
+    }
+  }
+  return cnt;
+}
+
+// dy [N, Hs, Ws, C] (Hs = 2H up, H / 2 down) -> dx with ring dxr, interior [N, H, W, C]
+template <typename T, bool UP>
+__global__ __launch_bounds__(256) void fir8_bwd_kernel(const u16* __restrict__ dy, u16* __restrict__ dx, int dxr, int N, int H, int W, int C) {
+  constexpr int S = UP ? 24 : 12;
+  const int G = C >> 2, Hs = UP ? 2 * H : H / 2, Ws = UP ? 2 * W : W / 2;
+  const int64_t total = (int64_t)N * H * W * G;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int g = (int)(i % G);
+    const int64_t pix = i / G;
+    const int n = (int)(pix / ((int64_t)H * W)), rem = (int)(pix - (int64_t)n * H * W), iy = rem / W, ix = rem - iy * W;
+    int yi[S], xi[S];
+    float yw[S], xw[S];
+    const int ny = fir8_bwd_taps<UP>(iy, H, yi, yw), nx = fir8_bwd_taps<UP>(ix, W, xi, xw);
+    const u16* b = dy + (int64_t)n * Hs * Ws * C + 4 * g;
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int r = 0; r < ny; ++r) {
+      const u16* row = b + (int64_t)yi[r] * Ws * C;
+      for (int t = 0; t < nx; ++t) {
+        float f[4];
+        ld4<T>(row + (int64_t)xi[t] * C, f);
+        const float wgt = yw[r] * xw[t];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = fmaf(wgt, f[e], o[e]);
+      }
+    }
+    *(uint2*)(dx + ring_off(n, iy, ix, H, W, dxr, C) + 4 * g) = pack4<T>(o[0], o[1], o[2], o[3]);
+  }
+}
+
+inline bool fir8_ok(const void* a, const void* b, int N, int H, int W, int C, int ring, int dtype, int hmin, bool even) {
+  return a && b && N > 0 && H >= hmin && W >= hmin && !(even && ((H & 1) || (W & 1))) && C > 0 && !(C & 3) && (ring == 0 || ring == 1) &&
+         (int64_t)N * (2 * H + 2) * (2 * W + 2) < (1ll << 31) && !(((uintptr_t)a | (uintptr_t)b) & 7) && (dtype == PMI_DT_F16 || dtype == PMI_DT_BF16);
+}
+
+}  // namespace
+
+extern "C" int pmi_fir8_down2(const void* x, int x_ring, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
+  if (!fir8_ok(x, y, N, H, W, C, x_ring, dtype, 4, true)) return PMI_ERR_ARG;
+  dim3 grid(grid_256((int64_t)N * (H / 2) * (W / 2) * (C / 4))), block(256);
+  if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(fir8_down2_kernel<BF16>, grid, block, 0, ST, (const u16*)x, x_ring, (u16*)y, N, H, W, C);
+  else hipLaunchKernelGGL(fir8_down2_kernel<F16>, grid, block, 0, ST, (const u16*)x, x_ring, (u16*)y, N, H, W, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_fir8_up2(const void* x, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
+  if (!fir8_ok(x, y, N, H, W, C, 0, dtype, 3, false)) return PMI_ERR_ARG;
+  dim3 grid(grid_256((int64_t)N * H * W * 4 * (C / 4))), block(256);
+  if (dtype == PMI_DT_BF16) hipLaunchKernelGGL(fir8_up2_kernel<BF16>, grid, block, 0, ST, (const u16*)x, (u16*)y, N, H, W, C);
+  else hipLaunchKernelGGL(fir8_up2_kernel<F16>, grid, block, 0, ST, (const u16*)x, (u16*)y, N, H, W, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_fir8_down2_bwd(const void* dy, void* dx, int dx_ring, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
+  if (!fir8_ok(dy, dx, N, H, W, C, dx_ring, dtype, 4, true)) return PMI_ERR_ARG;
+  dim3 grid(grid_256((int64_t)N * H * W * (C / 4))), block(256);
+  if (dtype == PMI_DT_BF16) hipLaunchKernelGGL((fir8_bwd_kernel<BF16, false>), grid, block, 0, ST, (const u16*)dy, (u16*)dx, dx_ring, N, H, W, C);
+  else hipLaunchKernelGGL((fir8_bwd_kernel<F16, false>), grid, block, 0, ST, (const u16*)dy, (u16*)dx, dx_ring, N, H, W, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}
+
+extern "C" int pmi_fir8_up2_bwd(const void* dy, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s) {
+  if (!fir8_ok(dy, dx, N, H, W, C, 0, dtype, 3, false)) return PMI_ERR_ARG;
+  dim3 grid(grid_256((int64_t)N * H * W * (C / 4))), block(256);
+  if (dtype == PMI_DT_BF16) hipLaunchKernelGGL((fir8_bwd_kernel<BF16, true>), grid, block, 0, ST, (const u16*)dy, (u16*)dx, 0, N, H, W, C);
+  else hipLaunchKernelGGL((fir8_bwd_kernel<F16, true>), grid, block, 0, ST, (const u16*)dy, (u16*)dx, 0, N, H, W, C);
+  PMI_CHECK_LAUNCH();
+  return PMI_OK;
+}

@@ -130,6 +130,17 @@ class PackedLinear:
         if up_phase and not self.split and kh == 3 and kw == 3 and self.n_p % 256 == 0 and self.cin_p % 64 == 0:
             self._frag[("up", 64)] = self._pack_up(packed.view(self.n_p, 3, 3, self.cin_p), 64, device, dt)
 
+    @classmethod
+    def from_device(cls, w16: torch.Tensor, bias: Optional[torch.Tensor], cout: int, cin: int, taps: int, dt: int) -> "PackedLinear":
+        """A layer whose B[n_p][taps * cin_p] was packed on the DEVICE (pmi_dip_pack_w) from weights an optimiser moves: engine/dip.py builds
+        one per convolution per forward, so `_frag` starts empty and no derived packing of older weights is ever served.  bias: fp32 [n_p]."""
+        lin = cls.__new__(cls)
+        lin.cout, lin.cin, lin.taps, lin.n_p = cout, cin, taps, w16.shape[0]
+        lin.cin_p = lin.cin_l = w16.shape[1] // taps
+        lin.split = lin.self_concat = lin.concat_inputs = False
+        lin.w, lin.b, lin.dt, lin._frag = w16, bias, dt, {}
+        return lin
+
     @staticmethod
     def _pack_up(w: torch.Tensor, ck: int, device, dt: int) -> torch.Tensor:
         """w: fp32 [N, dy, dx, Cin], unrounded -> the phase weights in the kernel's fragment order (see frag16_up)."""

@@ -10,3 +10,4 @@ from .super_resolution import SuperResolution
 from .monster_diffusion import MonsterDiffusion
 from .glide_clip import GlideCLIP
 from .owlvit import OWLViT, OWLViTEncodings, OWLViTPredictions
+from .deep_image_prior import DeepImagePrior
