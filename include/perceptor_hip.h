@@ -683,6 +683,39 @@ int pmi_fir8_up2(const void* x, void* y, int N, int H, int W, int C, int dtype, 
 int pmi_fir8_down2_bwd(const void* dy, void* dx, int dx_ring, int N, int H, int W, int C, int dtype, pmi_stream_t s);
 int pmi_fir8_up2_bwd(const void* dy, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s);
 
+/* ---- DPT depth decoder (dpt.hip): the memory-bound steps between the convolutions of models.MidasDepth ----
+ * Tensors are NHWC 16-bit (dtype = f16 / bf16) unless stated, C a multiple of 8, pointers 16-byte aligned; fp32 arithmetic, one rounding at
+ * the store.  No atomics: two runs are bit-equal.  Bad arguments return PMI_ERR_ARG without a launch.
+ * pmi_bilinear2_ac_fwd: y [N, 2H, 2W, C] = F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True) (+ r, NULL or a tensor on the
+ *   OUTPUT grid: the other summand of the next fusion block).  Output index o reads source o (L - 1) / (2L - 1); L = 1 copies.  H, W <= 16384.
+ *   (pmi_upsample_bilinear2 is align_corners=False: another operator.)
+ * pmi_bilinear2_ac_bwd: the exact adjoint in gather form, g [N, 2H, 2W, C] -> dx [N, H, W, C]; H, W are the FORWARD input's size.
+ * pmi_depth_to_space: x [N, H, W, k k C] with columns ordered (ky, kx, c) -> y [N, kH, kW, C], y[n, k y + ky, k x + kx, c] = x[n, y, x, (ky, kx, c)]
+ *   + bias[c] (fp32, NULL: none); k in {2, 4}.  With the GEMM to k k C columns before it this is ConvTranspose2d(C', C, k, stride=k).
+ * pmi_space_to_depth: the inverse permutation (the adjoint's first step), y -> x; after pmi_depth_to_space without bias it returns x bit for bit.
+ * pmi_dpt_tap_split: x fp32 [N][T][W] -> tok 16-bit [N (T - 1)][W] (rows 1 .. T - 1) and cls 16-bit [N][W] (row 0).  W % 4 == 0, T >= 2.
+ * pmi_dpt_tap_join: d_tok fp32 [N (T - 1)][W], d_cls fp32 [N][W] -> out fp32 [N][T][W].
+ * pmi_dpt_tap_add: out32 = a + b (fp32, n values, n % 4 == 0) and out16 = the same sum rounded once.
+ * pmi_dpt_colsum: x 16-bit [N][P][W] -> out fp32 [N][W] = sum over p, rows p = j (mod 4) summed in order into s_j, then (s0 + s1) + (s2 + s3).
+ *   W even, x 4-byte aligned, N <= 65535.
+ * pmi_dpt_relu_bwd: dz = g (y > 0 ? 1 : 0) (+ r, NULL or like g); y is the ReLU's output OR its input (the masks agree), n % 8 == 0.
+ * pmi_dpt_head_fwd: h 16-bit [P][32] (post-ReLU), w fp32 [32], b fp32 [1] -> out fp32 [P] = -relu(w . h + b) (NCHW with one channel); the fp32
+ *   pointers of both head kernels 4-byte aligned.
+ * pmi_dpt_head_bwd: dh 16-bit [P][32], dh[p][c] = -scale dout[p] (out[p] < 0) w[c] (h[p][c] > 0): out < 0 exactly where the pre-ReLU value was
+ *   positive, and the mask of the ReLU that produced h is folded in. */
+int pmi_bilinear2_ac_fwd(const void* x, const void* r, void* y, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_bilinear2_ac_bwd(const void* g, void* dx, int N, int H, int W, int C, int dtype, pmi_stream_t s);
+int pmi_depth_to_space(const void* x, const float* bias, void* y, int N, int H, int W, int C, int k, int dtype, pmi_stream_t s);
+int pmi_space_to_depth(const void* y, void* x, int N, int H, int W, int C, int k, int dtype, pmi_stream_t s);
+int pmi_dpt_tap_split(const float* x, void* tok, void* cls, int N, int T, int W, int dtype, pmi_stream_t s);
+int pmi_dpt_tap_join(const float* d_tok, const float* d_cls, float* out, int N, int T, int W, pmi_stream_t s);
+int pmi_dpt_tap_add(const float* a, const float* b, float* out32, void* out16, int64_t n, int dtype, pmi_stream_t s);
+int pmi_dpt_colsum(const void* x, float* out, int N, int P, int W, int dtype, pmi_stream_t s);
+int pmi_dpt_relu_bwd(const void* g, const void* y, const void* r, void* dz, int64_t n, int dtype, pmi_stream_t s);
+int pmi_dpt_head_fwd(const void* h, const float* w, const float* b, float* out, int64_t P, int dtype, pmi_stream_t s);
+int pmi_dpt_head_bwd(const float* dout, const float* out, const void* h, const float* w, void* dh, int64_t P, float scale, int dtype,
+                     pmi_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

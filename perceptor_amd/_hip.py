@@ -233,6 +233,18 @@ _PROTOS = {
     "pmi_fir8_up2": ([_P, _P, _I, _I, _I, _I, _I, _P],),
     "pmi_fir8_down2_bwd": ([_P, _P, _I, _I, _I, _I, _I, _I, _P],),
     "pmi_fir8_up2_bwd": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    # DPT depth decoder of models.MidasDepth (dpt.hip)
+    "pmi_bilinear2_ac_fwd": ([_P, _P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_bilinear2_ac_bwd": ([_P, _P, _I, _I, _I, _I, _I, _P],),
+    "pmi_depth_to_space": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],),
+    "pmi_space_to_depth": ([_P, _P, _I, _I, _I, _I, _I, _I, _P],),
+    "pmi_dpt_tap_split": ([_P, _P, _P, _I, _I, _I, _I, _P],),
+    "pmi_dpt_tap_join": ([_P, _P, _P, _I, _I, _I, _P],),
+    "pmi_dpt_tap_add": ([_P, _P, _P, _P, _L, _I, _P],),
+    "pmi_dpt_colsum": ([_P, _P, _I, _I, _I, _I, _P],),
+    "pmi_dpt_relu_bwd": ([_P, _P, _P, _P, _L, _I, _P],),
+    "pmi_dpt_head_fwd": ([_P, _P, _P, _P, _L, _I, _P],),
+    "pmi_dpt_head_bwd": ([_P, _P, _P, _P, _P, _L, _F, _I, _P],),
 }
 
 

@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libperceptor_hip.so")
-SOURCES = ["igemm.hip", "conv3x3.hip", "conv_wd.hip", "conv_up_wd.hip", "gemm_wd.hip", "norm.hip", "attn.hip", "attn_flash.hip", "elementwise.hip", "clip.hip", "f32gemm.hip", "sampling.hip", "backward.hip", "resnet.hip", "losses.hip", "vgg.hip", "lpips.hip", "rrdb.hip", "fir.hip", "disc.hip", "jpeg.hip", "glide.hip", "owlvit.hip", "dip.hip"]
+SOURCES = ["igemm.hip", "conv3x3.hip", "conv_wd.hip", "conv_up_wd.hip", "gemm_wd.hip", "norm.hip", "attn.hip", "attn_flash.hip", "elementwise.hip", "clip.hip", "f32gemm.hip", "sampling.hip", "backward.hip", "resnet.hip", "losses.hip", "vgg.hip", "lpips.hip", "rrdb.hip", "fir.hip", "disc.hip", "jpeg.hip", "glide.hip", "owlvit.hip", "dip.hip", "dpt.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC"]
 # per-file additions.  conv_wd.hip: no SLP vectorisation -- the vectoriser packs the patch staging's f32 arithmetic into v_pk_fma_f32 /
 # v_pk_mul_f32, which cost MORE vector-issue time beside MFMAs than the two scalar ops they replace (MI355X_MICROARCH.md, per-instruction

@@ -102,6 +102,44 @@ def hf_vision_state_dict_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
     return S
 
 
+def from_timm_vit_state_dict(sd: Dict[str, torch.Tensor], prefix: str = "") -> Dict[str, torch.Tensor]:
+    """timm's VisionTransformer keys under ``prefix`` (``cls_token``, ``pos_embed``, ``patch_embed.proj.{weight,bias}``,
+    ``blocks.{i}.{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}``; ``norm.*`` and ``head.*`` are not read) -> the OpenAI-CLIP names this
+    engine packs, for VitEngine(..., quick_gelu=False, ln_eps=1e-6, pre_ln=False, pooled_head=False).  timm's patch convolution has a bias and
+    CLIP's has none: it is added to the patch rows of the positional embedding here (x = conv(p) + b + pos = conv(p) + (pos + b))."""
+    g = lambda k: sd[prefix + k].detach().float()
+    pos = g("pos_embed")
+    if pos.ndim != 3 or pos.shape[0] != 1:
+        raise ValueError(f"pos_embed must be [1, T, width], got {tuple(pos.shape)}")
+    pos = pos[0].clone()
+    pos[1:] += g("patch_embed.proj.bias")[None, :]
+    out = {"class_embedding": g("cls_token").reshape(-1), "conv1.weight": g("patch_embed.proj.weight"), "positional_embedding": pos}
+    i = 0
+    while f"{prefix}blocks.{i}.norm1.weight" in sd:
+        a, b = f"blocks.{i}.", f"transformer.resblocks.{i}."
+        out[b + "attn.in_proj_weight"], out[b + "attn.in_proj_bias"] = g(a + "attn.qkv.weight"), g(a + "attn.qkv.bias")
+        for src, dst in (("attn.proj", "attn.out_proj"), ("norm1", "ln_1"), ("norm2", "ln_2"), ("mlp.fc1", "mlp.c_fc"), ("mlp.fc2", "mlp.c_proj")):
+            out[b + dst + ".weight"], out[b + dst + ".bias"] = g(a + src + ".weight"), g(a + src + ".bias")
+        i += 1
+    return out
+
+
+def timm_vit_state_dict_shapes(cfg) -> Dict[str, Tuple[int, ...]]:
+    """The keys from_timm_vit_state_dict reads, with timm's shapes; cfg = (image, patch, width, layers, heads, _)."""
+    res, patch, width, layers = cfg[:4]
+    S = {"cls_token": (1, 1, width), "pos_embed": (1, (res // patch) ** 2 + 1, width),
+         "patch_embed.proj.weight": (width, 3, patch, patch), "patch_embed.proj.bias": (width,)}
+    for i in range(layers):
+        p = f"blocks.{i}."
+        S[p + "norm1.weight"] = (width,); S[p + "norm1.bias"] = (width,)
+        S[p + "attn.qkv.weight"] = (3 * width, width); S[p + "attn.qkv.bias"] = (3 * width,)
+        S[p + "attn.proj.weight"] = (width, width); S[p + "attn.proj.bias"] = (width,)
+        S[p + "norm2.weight"] = (width,); S[p + "norm2.bias"] = (width,)
+        S[p + "mlp.fc1.weight"] = (4 * width, width); S[p + "mlp.fc1.bias"] = (4 * width,)
+        S[p + "mlp.fc2.weight"] = (width, 4 * width); S[p + "mlp.fc2.bias"] = (width,)
+    return S
+
+
 class _Lin:
     """Forward weights + the transposed copy used by the input-gradient GEMM."""
 
@@ -111,8 +149,14 @@ class _Lin:
 
 
 class VitEngine:
-    def __init__(self, cfg, state_dict, device, dtype="bf16", quick_gelu=True):
+    def __init__(self, cfg, state_dict, device, dtype="bf16", quick_gelu=True, ln_eps=1e-5, pre_ln=True, pooled_head=True,
+                 norm=(CLIP_MEAN, CLIP_STD)):
+        """norm = (mean, std) per channel of the stem's normalisation (MiDaS: 0.5, 0.5).
+        ln_eps: every LayerNorm's epsilon (timm: 1e-6).  pre_ln=False: no ln_pre between the embedding and the first block (timm's tower has
+        none).  pooled_head=False: no ln_post / proj (their keys are not read): forward() returns None for the embedding, and the gradient
+        enters through backward_tokens / backward_taps only."""
         self.cfg, self.device = cfg, torch.device(device)
+        self.ln_eps, self.pre_ln, self.pooled_head = float(ln_eps), bool(pre_ln), bool(pooled_head)
         self.dt = _hip.dtype_code(dtype)
         # fp16 cannot hold ~1e-6 gradients: scale the loss gradient up and the image gradient back down
         self.gscale = 1.0 if self.dt == _hip.DT_BF16 else 65536.0
@@ -128,9 +172,12 @@ class VitEngine:
         wc_p[:, :k] = wc
         self.conv1 = _Lin(wc_p, None, dt, dev)
         self.cls, self.pos = f32("class_embedding"), f32("positional_embedding")
-        self.ln_pre = (f32("ln_pre.weight"), f32("ln_pre.bias"))
-        self.ln_post = (f32("ln_post.weight"), f32("ln_post.bias"))
-        self.proj = _Lin(sd["proj"].detach().float().t().contiguous(), None, dt, dev)
+        if res % patch or tuple(self.pos.shape) != ((res // patch) ** 2 + 1, width):
+            raise ValueError(f"the position grid must be res / patch = {res}/{patch}: expected a positional embedding "
+                             f"{((res // patch) ** 2 + 1, width)}, got {tuple(self.pos.shape)} (positional embeddings are not resampled)")
+        self.ln_pre = (f32("ln_pre.weight"), f32("ln_pre.bias")) if self.pre_ln else None
+        self.ln_post = (f32("ln_post.weight"), f32("ln_post.bias")) if self.pooled_head else None
+        self.proj = _Lin(sd["proj"].detach().float().t().contiguous(), None, dt, dev) if self.pooled_head else None
         self.blocks = []
         for i in range(layers):
             p = f"transformer.resblocks.{i}."
@@ -140,8 +187,8 @@ class VitEngine:
                 out=_Lin(sd[p + "attn.out_proj.weight"].float(), sd[p + "attn.out_proj.bias"], dt, dev),
                 fc=_Lin(sd[p + "mlp.c_fc.weight"].float(), sd[p + "mlp.c_fc.bias"], dt, dev),
                 pr=_Lin(sd[p + "mlp.c_proj.weight"].float(), sd[p + "mlp.c_proj.bias"], dt, dev)))
-        self.mean = torch.tensor(CLIP_MEAN, device=dev)
-        self.std = torch.tensor(CLIP_STD, device=dev)
+        self.mean = torch.tensor(norm[0], dtype=torch.float32, device=dev)
+        self.std = torch.tensor(norm[1], dtype=torch.float32, device=dev)
         self.output_dim = out
         self.saved = None
 
@@ -151,7 +198,7 @@ class VitEngine:
         y16 = torch.empty((m, d), dtype=_hip.TORCH_DTYPE[self.dt], device=dev) if want16 else None
         y32 = torch.empty((m, d), dtype=torch.float32, device=dev) if want32 else None
         mr = torch.empty((2, m), dtype=torch.float32, device=dev)
-        call("pmi_layernorm_fwd", ptr(x), ld, ptr(gb[0]), ptr(gb[1]), ptr(y16), ptr(y32), ptr(mr), m, d, 1e-5, self.dt)
+        call("pmi_layernorm_fwd", ptr(x), ld, ptr(gb[0]), ptr(gb[1]), ptr(y16), ptr(y32), ptr(mr), m, d, self.ln_eps, self.dt)
         return y16, y32, mr
 
     def _ln_bwd(self, dy, dy_ld, x, gb, mr, gres, m, d, row_stride=1, g32=None, g16=None, want32=True, want16=True):
@@ -171,7 +218,7 @@ class VitEngine:
         x = torch.empty((m, d), dtype=torch.float32, device=dev)
         y16 = torch.empty((m, d), dtype=_hip.TORCH_DTYPE[self.dt], device=dev)
         mr = torch.empty((2, m), dtype=torch.float32, device=dev)
-        call("pmi_layernorm_fwd_slabs", ptr(ws), sk, m * d, ptr(bias), ptr(residual), ptr(x), ptr(gb[0]), ptr(gb[1]), ptr(y16), ptr(mr), m, d, 1e-5, self.dt)
+        call("pmi_layernorm_fwd_slabs", ptr(ws), sk, m * d, ptr(bias), ptr(residual), ptr(x), ptr(gb[0]), ptr(gb[1]), ptr(y16), ptr(mr), m, d, self.ln_eps, self.dt)
         return x, y16, mr
 
     def _ln_bwd_any(self, dy, x, gb, mr, gres, m, d):
@@ -199,6 +246,8 @@ class VitEngine:
         pe = ops.igemm(col, self.conv1.fwd, out_f32=True)
         x0 = torch.empty((n, t, width), dtype=torch.float32, device=dev)
         call("pmi_vit_assemble", ptr(pe), ptr(self.cls), ptr(self.pos), ptr(x0), n, t, width, 0)
+        if not self.pre_ln:
+            return x0, x0.view(n * t, width), None
         _, x, mr_pre = self._ln(x0, width, self.ln_pre, n * t, width, want16=False, want32=True)
         return x0, x, mr_pre
 
@@ -208,21 +257,27 @@ class VitEngine:
         dt, dev = self.dt, self.device
         n = sv["n"]
         t = (res // patch) ** 2 + 1
-        _, g0 = self._ln_bwd(g32, width, sv["x0"], self.ln_pre, sv["mr_pre"], None, n * t, width, want32=False)
+        if self.pre_ln:
+            _, g0 = self._ln_bwd(g32, width, sv["x0"], self.ln_pre, sv["mr_pre"], None, n * t, width, want32=False)
+        else:                                     # no ln_pre: its adjoint is the identity, the GEMM reads the gradient as a 16-bit operand
+            g0 = torch.empty((n * t, width), dtype=_hip.TORCH_DTYPE[dt], device=dev)
+            call("pmi_cast_f32_to_16", ptr(g32), ptr(g0), n * t * width, ACT_NONE, dt)
         dcol = torch.empty((n * (t - 1), self.kp), dtype=torch.float32, device=dev)
         ops.bgemm(g0, self.conv1.bwd.w, dcol, M=t - 1, N=self.kp, K=width, lda=width, ldb=width, ldd=self.kp, batch=n, batch_inner=1,
                   sA=(t * width, 0), sB=(0, 0), sD=((t - 1) * self.kp, 0), dt=dt, a_off=width)
         dres = torch.empty((n, 3, res, res), dtype=torch.float32, device=dev)
-        call("pmi_unpatchify", ptr(dcol), ptr(self.std), ptr(dres), n, res, patch, self.kp, 1.0 / self.gscale)
+        call("pmi_unpatchify", ptr(dcol), ptr(self.std), ptr(dres), n, res, patch, self.kp, 1.0 / (self.gscale * sv.get("grad_scale", 1.0)))
         if record is not None:
             record.update(g0=g0, dcol=dcol)
         return _resize_backward(dres, sv["in_hw"])
 
     # ---- forward --------------------------------------------------------------------------------------
     @torch.no_grad()
-    def forward(self, images: torch.Tensor, save: bool = False, features: bool = False):
+    def forward(self, images: torch.Tensor, save: bool = False, features: bool = False, taps=None):
         """images NCHW fp32 in [0,1] (any size) -> un-normalised embeddings [N, out_dim] fp32
-        (features=True: also the last hidden state [N, T, width] and the post-LayerNorm class token [N, width], both fp32)."""
+        (features=True: also the last hidden state [N, T, width] and the post-LayerNorm class token [N, width], both fp32).
+        taps = (i0, i1, ...), ascending block indices: returns (embeddings or None without a pooled head, [the fp32 residual stream
+        [N, T, width] at the output of those blocks]) -- what a forward hook on ``blocks[i]`` sees; no copy, the tensors the walk made."""
         if not images.is_cuda:
             raise RuntimeError("VitEngine runs on a HIP device only (no CPU fallback)")
         res, patch, width, layers, heads, out = self.cfg
@@ -233,8 +288,15 @@ class VitEngine:
         t = g * g + 1
         m = n * t
         d = width // heads
+        if taps is not None:
+            taps = tuple(int(i) for i in taps)
+            if features or not taps or list(taps) != sorted(set(taps)) or taps[0] < 0 or taps[-1] >= layers:
+                raise ValueError(f"taps must be ascending block indices in [0, {layers}) (and not combined with features=True), got {taps}")
+        tapped = []
         x0, x, mr_pre = self._embed(images)
         sv = dict(in_hw=tuple(images.shape[2:]), n=n, x0=x0, mr_pre=mr_pre, layers=[]) if save else None
+        if save and taps is not None:
+            sv["taps"] = taps
         fuse = width % 256 == 0 and width <= 2048            # split-K reduce of the MLP's last GEMM + the next block's LayerNorm in one pass
         nxt = None                                           # (h, mr1) of this block when the previous block's tail already produced them
         for bi, blk in enumerate(self.blocks):
@@ -269,12 +331,23 @@ class VitEngine:
                     L["qkv"], L["p"] = kept
                 sv["layers"].append(L)
             x = x_out
+            if taps is not None and bi in taps:
+                tapped.append(x.view(n, t, width))
+        if not self.pooled_head:
+            if save:
+                sv.update(x_final=x, mr_post=None)
+                self.saved = sv
+            if taps is not None:
+                return None, tapped
+            return (None, x.view(n, t, width), None) if features else None
         y16, y32, mr_post = self._ln(x, t * width, self.ln_post, n, width, want32=features)         # cls token rows only
         emb = ops.igemm(y16, self.proj.fwd, out_f32=True)
         if save:
             sv.update(x_final=x, mr_post=mr_post)
             self.saved = sv
         emb = emb[:, :out] if emb.shape[1] != out else emb
+        if taps is not None:
+            return emb, tapped
         return (emb, x.view(n, t, width), y32) if features else emb
 
     # ---- input gradient -----------------------------------------------------------------------------------
@@ -287,6 +360,8 @@ class VitEngine:
         sv = self.saved
         if sv is None:
             raise RuntimeError("call forward(images, save=True) before backward()")
+        if not self.pooled_head:
+            raise RuntimeError("this tower has no pooled head: the gradient enters through backward_tokens() or backward_taps()")
         res, patch, width, layers, heads, out = self.cfg
         dt, dev = self.dt, self.device
         tdt = _hip.TORCH_DTYPE[dt]
@@ -320,9 +395,38 @@ class VitEngine:
         call("pmi_cast_f32_to_16", ptr(g32), ptr(g16), m * width, ACT_NONE, self.dt)
         return self._backward_blocks(g32, g16, sv, record)
 
-    def _backward_blocks(self, g32, g16, sv, record):
-        """The walk both entries share: (g32, g16) = the gradient at the last block's output (times gscale), fp32 and as the 16-bit GEMM
-        operand -> through the blocks, last first, and the stem, to the images."""
+    @torch.no_grad()
+    def backward_taps(self, d_taps, record: Optional[dict] = None, scale: float = 1.0) -> torch.Tensor:
+        """d_taps: dL/d(tap) * self.gscale * scale for each tap forward(..., save=True, taps=) returned, in that order, fp32 [N, T, width]
+        (scale: a further power of two the caller's f16 gradients carry, ops.f16_grad_scale; the stem divides it out with gscale)
+        ->  dL/d(images), fp32 NCHW.  The walk starts at the LAST tap's block (blocks above it feed nothing that is differentiated) and
+        adds each earlier tap's gradient where it reaches that block's output.  One tap at the last block is backward_tokens()."""
+        sv = self.saved
+        if sv is None:
+            raise RuntimeError("call forward(images, save=True, taps=...) before backward_taps()")
+        res, patch, width, layers, heads, out = self.cfg
+        t = (res // patch) ** 2 + 1
+        m = sv["n"] * t
+        taps = sv.get("taps")
+        if taps is None:
+            raise RuntimeError("the saved forward took no taps: call forward(images, save=True, taps=...)")
+        if len(d_taps) != len(taps):
+            raise ValueError(f"{len(taps)} taps were taken, {len(d_taps)} gradients given")
+        for d in d_taps:
+            if d.dtype != torch.float32 or tuple(d.shape) != (sv["n"], t, width):
+                raise ValueError(f"every tap gradient must be fp32 [{sv['n']}, {t}, {width}]")
+        g32 = d_taps[-1].contiguous().view(m, width)
+        g16 = torch.empty((m, width), dtype=_hip.TORCH_DTYPE[self.dt], device=self.device)
+        call("pmi_cast_f32_to_16", ptr(g32), ptr(g16), m * width, ACT_NONE, self.dt)
+        inject = {i: d.contiguous().view(m, width) for i, d in zip(taps[:-1], d_taps[:-1])}
+        if scale != 1.0:
+            sv["grad_scale"] = float(scale)
+        return self._backward_blocks(g32, g16, sv, record, top=taps[-1], inject=inject)
+
+    def _backward_blocks(self, g32, g16, sv, record, top=None, inject=None):
+        """The walk all entries share: (g32, g16) = the gradient at block ``top``'s output (the last block's by default; times gscale), fp32
+        and as the 16-bit GEMM operand -> through the blocks, ``top`` first, and the stem, to the images.  inject = {block index: fp32
+        [m, width]}: added to the gradient where the walk reaches that block's output (pmi_dpt_tap_add: the sum and its 16-bit copy)."""
         res, patch, width, layers, heads, out = self.cfg
         dt = self.dt
         n = sv["n"]
@@ -330,7 +434,15 @@ class VitEngine:
         m = n * t
         if record is not None:
             record.update(g32=[g32], gm32=[])
-        for blk, L in zip(reversed(self.blocks), reversed(sv["layers"])):
+        top = len(self.blocks) - 1 if top is None else top
+        for bi in range(top, -1, -1):
+            blk, L = self.blocks[bi], sv["layers"][bi]
+            if inject and bi in inject:
+                s32, s16 = torch.empty_like(g32), torch.empty_like(g16)
+                call("pmi_dpt_tap_add", ptr(g32), ptr(inject[bi]), ptr(s32), ptr(s16), g32.numel(), dt)
+                g32, g16 = s32, s16
+                if record is not None:
+                    record.setdefault("g32_joined", {})[bi] = g32
             # ---- MLP branch
             if ops.fused_mlp_epilogues(blk["pr"].bwd, m):    # dh * act'(h_pre) in the GEMM epilogue
                 dh = ops.igemm(g16, blk["pr"].bwd, act_grad_of=L["hpre"], act_grad=self.act)    # [m, 4w]

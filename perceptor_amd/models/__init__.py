@@ -11,3 +11,4 @@ from .monster_diffusion import MonsterDiffusion
 from .glide_clip import GlideCLIP
 from .owlvit import OWLViT, OWLViTEncodings, OWLViTPredictions
 from .deep_image_prior import DeepImagePrior
+from .midas_depth import MidasDepth
